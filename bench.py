@@ -7,16 +7,24 @@ One step = SAM2LightningModule.training_step on one clip per rank (forward over
 the flat gradient arena (N > 1) + grad-norm clip + AdamW.  Inputs are resident
 in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
-The roofline (N = 1): before it touches the GPU, bench.py runs a copy of itself under
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the K timed
+steps, the result line.  --dump-outputs DIR then writes what the last timed step handed its caller
+(loss, logged loss terms, per-frame predictions, gradients, updated parameters) as DIR/<name>.npy,
+float32, larger arrays as a fixed seeded sample; the inputs depend on the arguments alone, so two
+builds can be compared output for output.  --full adds everything else this file measures: the
+roofline below, the validation IoU on a held-out clip and the CPU baseline.
+
+The roofline (--full, N = 1): before it touches the GPU, bench.py runs a copy of itself under
 `rocprofv3 --kernel-trace` (--trace-child: same workload, --trace-steps timed replays between the
 trace markers); per-family and dominant-kernel durations come from that trace of the timed replays,
 algorithmic flops per launch from the in-library profiler's records of one eager step after the
 timed region.  The event-bracketed durations of that eager step ride along under
 roofline.event_based.  --trace-out writes the trace's per-kernel CSV (tools/step_profile.py reads it
-with the same bench line).  --no-trace skips the traced run.
+with the same bench line).  --no-trace skips the traced run.  --no-trace, --no-prof and
+--cpu-baseline 0 switch single legs of --full off; without --full none of the legs runs.
 """
 from __future__ import annotations
 
@@ -73,7 +81,21 @@ def parse():
     ap.add_argument("--trace-steps", type=int, default=5, help="timed steps of the traced run")
     ap.add_argument("--trace-out", default=None, help="write the traced run's per-kernel CSV here")
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the rocprofv3-traced roofline, the "
+                         "profiled eager step, the validation IoU and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        for opt in ("shape_table", "kernel_table", "trace_out"):
+            if getattr(args, opt):
+                ap.error(f"--{opt.replace('_', '-')} reads the profiled step: run it with --full")
+        # a plain run: the timed steps alone (the traced child of a --full run is one too)
+        args.no_trace = args.no_prof = True
+        args.cpu_baseline = 0
     if args.config == 5:
         args.frames = 16
         if args.dtype is None:
@@ -233,9 +255,8 @@ def traced_run(args):
         return None, 0, "rocprofv3 not found"
     tdir = tempfile.mkdtemp(prefix="s2h_trace_")
     cmd = [prof, "--kernel-trace", "-f", "csv", "-d", tdir, "-o", "kt", "--", sys.executable,
-           os.path.abspath(__file__), "--trace-child", "--no-trace", "--no-prof", "--cpu-baseline", "0",
-           "--steps", str(args.trace_steps), "--warmup", "2", "--size", args.size, "--image-size",
-           str(args.image_size), "--frames", str(args.frames), "--objects", str(args.objects), "--dtype",
+           os.path.abspath(__file__), "--trace-child", "--steps", str(args.trace_steps), "--warmup", "2",
+           "--size", args.size, "--image-size", str(args.image_size), "--frames", str(args.frames), "--objects", str(args.objects), "--dtype",
            args.dtype, "--config", str(args.config), "--trainable", args.trainable]
     if args.dropout is not None:
         cmd += ["--dropout", str(args.dropout)]
@@ -460,6 +481,59 @@ def cpu_baseline(args):
                       f"{threads} threads"}
 
 
+DUMP_SAMPLE = 1 << 18  # elements kept of a larger array: 1 MiB each in float32, far below 64 MB over all files
+
+
+def sample_indices(numel):
+    """DUMP_SAMPLE distinct, increasing indices into an array of `numel` elements: one from each of
+    DUMP_SAMPLE equal strata, its place in the stratum drawn from numpy's frozen legacy generator
+    seeded by `numel` alone -- the same elements for every build, whatever its torch"""
+    import numpy as np
+    base = np.arange(DUMP_SAMPLE, dtype=np.int64) * numel // DUMP_SAMPLE
+    return base + np.random.RandomState(numel % 2**32).randint(0, numel // DUMP_SAMPLE, DUMP_SAMPLE)
+
+
+def dump_outputs(path, loss, module):
+    """What the last timed step handed its caller, as <path>/<name>.npy in float32: the returned loss,
+    the logged loss terms, every tensor of the per-frame outputs (frames stacked where their shapes
+    agree), and the step's effect on the model -- the gradient region and the updated fp32 parameters
+    of the arena.  An array of more than DUMP_SAMPLE elements is written as the sample
+    flat[sample_indices(numel)], so two builds sample the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss}
+    for name, v in module.logged.items():
+        if torch.is_tensor(v):
+            arrays["logged_" + name.replace("/", "_")] = v
+    per_key = {}
+    for t, fr in enumerate(module.last_outputs or []):
+        owned = set()  # storage an earlier key of this frame already names (multistep_pred_masks = pred_masks, ...)
+        for key, v in fr.items():
+            v = v[0] if isinstance(v, (list, tuple)) and len(v) == 1 else v
+            if torch.is_tensor(v) and (v.data_ptr(), tuple(v.shape)) not in owned:
+                owned.add((v.data_ptr(), tuple(v.shape)))
+                per_key.setdefault(key, []).append((t, v))
+    for key, items in per_key.items():
+        if len({tuple(v.shape) for _, v in items}) == 1:
+            arrays["frames_" + key] = torch.stack([v.detach().float() for _, v in items])
+        else:
+            for t, v in items:
+                arrays[f"frame{t}_{key}"] = v
+    arena = module.model.arena
+    arrays["grad_arena"] = arena.grad_region()
+    arrays["param_arena"] = arena.data
+    total = 0
+    for name, v in arrays.items():
+        flat = v.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = sample_indices(flat.numel())
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.float().cpu().numpy().astype(np.float32, copy=False)
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a if flat.numel() != v.numel() else a.reshape(tuple(v.shape)))
+    assert total <= 64 * 10**6, f"--dump-outputs wrote {total} bytes"
+
+
 def spawn_ranks(n):
     """`bench.py --gpus N` outside torchrun: start N rank processes (one per GPU, RCCL over
     127.0.0.1) before this parent touches the GPU, wait for all, exit with the worst status.
@@ -562,6 +636,8 @@ def main():
     if not math.isfinite(loss_val):
         print(f"ERROR: non-finite training loss {loss_val} in the timed steps", file=sys.stderr)
         sys.exit(3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, module)
     roof = None
     if not args.no_prof:
         if graph:
@@ -627,13 +703,15 @@ def main():
         return
 
     # validation IoU (eval/eval.py formulas, in-loop) on a held-out synthetic clip per rank
-    val_clip = make_clip(100_000 + rank, args.frames, args.image_size, args.objects, args.objects)
-    module.validation_step(sam2_collate_fn([val_clip]).to(device))
-    val_iou = float(module.last_eval["avg_scores"]["iou"])
-    if world > 1:
-        t = torch.tensor([val_iou], device=device)
-        dist.all_reduce(t)
-        val_iou = float(t.item()) / world
+    val_iou = None
+    if args.full:
+        val_clip = make_clip(100_000 + rank, args.frames, args.image_size, args.objects, args.objects)
+        module.validation_step(sam2_collate_fn([val_clip]).to(device))
+        val_iou = float(module.last_eval["avg_scores"]["iou"])
+        if world > 1:
+            t = torch.tensor([val_iou], device=device)
+            dist.all_reduce(t)
+            val_iou = float(t.item()) / world
     result = {
         "metric": "training clip-frames/sec (512^2 8-frame, Hiera-B+)",
         "value": round(value, 3),
@@ -660,7 +738,7 @@ def main():
         "final_loss": round(loss_val, 5),
         # eval.py IoU of the category-merged masks on held-out synthetic clips (random-init weights
         # after `steps` fine-tuning steps: a pipeline check, not a model-quality number)
-        "val_iou": round(val_iou, 5),
+        "val_iou": None if val_iou is None else round(val_iou, 5),
     }
     if rank == 0 and world == 1 and args.cpu_baseline:
         try:

@@ -3,9 +3,10 @@
 #   bash tools/gpu_drop0.sh TAG
 set -o pipefail
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 TAG=${1:-drop0}
-timeout -k 10 600 python3 bench.py --dropout 0 --cpu-baseline 0 --trace-steps 10 --trace-out gpurun_out/${TAG}_kernel_stats.csv > gpurun_out/${TAG}_bench.log 2> gpurun_out/${TAG}_bench.err || { echo BENCH_FAILED; tail -20 gpurun_out/${TAG}_bench.err; exit 1; }
-cut -c1-200 gpurun_out/${TAG}_bench.log
-python3 tools/step_profile.py gpurun_out/${TAG}_kernel_stats.csv gpurun_out/${TAG}_kernel_stats_sorted.csv --steps 10 --bench gpurun_out/${TAG}_bench.log > gpurun_out/${TAG}_step_profile.txt || exit 1
-head -12 gpurun_out/${TAG}_step_profile.txt
+timeout -k 10 600 python3 bench.py --full --dropout 0 --cpu-baseline 0 --trace-steps 10 --trace-out "$OUT/${TAG}_kernel_stats.csv" > "$OUT/${TAG}_bench.log" 2> "$OUT/${TAG}_bench.err" || { echo BENCH_FAILED; tail -20 "$OUT/${TAG}_bench.err"; exit 1; }
+cut -c1-200 "$OUT/${TAG}_bench.log"
+python3 tools/step_profile.py "$OUT/${TAG}_kernel_stats.csv" "$OUT/${TAG}_kernel_stats_sorted.csv" --steps 10 --bench "$OUT/${TAG}_bench.log" > "$OUT/${TAG}_step_profile.txt" || exit 1
+head -12 "$OUT/${TAG}_step_profile.txt"
