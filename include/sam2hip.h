@@ -429,7 +429,7 @@ int s2h_linear_dgrad_ln_bwd(int M, int N, int K, const void* G, int64_t ldg, con
 /* dgamma += sum_b part[b][0:C], dbeta += sum_b part[b][C:2C] over nb partial rows of 2C floats. */
 int s2h_ln_wgrad_finalize(int nb, int C, const float* part, float* dgamma, float* dbeta, hipStream_t st);
 
-/* Per-object MLP heads under no_grad in ONE launch (bf16): for each of nheads (<= 4) heads, rows
+/* Per-object MLP heads under no_grad in ONE launch (bf16): for each of nheads (<= 8) heads, rows
  * x[h] [M, dims[4h]] (row stride ldx[h]) through nl[h] (<= 3) Linear layers w[3h + l]
  * [dims[4h+l+1], dims[4h+l]] (+ fp32 bias b[3h + l] or NULL), ReLU between layers, act_last[h]
  * (S2HAct) after the last, into y[h] [M, dims[4h + nl]] (row stride ldy[h]); widths <= 256 (hidden
@@ -585,6 +585,29 @@ int s2h_convt2_store(int dt, int B, int H, int W, int Co, const void* Y, const f
  * sum_c hyper[b][c] post[b][p][c] (fp32 sum, bf16 store); pre / post [B, 2H, 2W, 32], masks [B, 2H * 2W]. */
 int s2h_convt2_tail(int dt, int B, int H, int W, int Co, const void* Y, const float* bias, const void* add,
                     int add_bcast, const void* hyper, void* pre, void* post, void* masks, hipStream_t st);
+/* s2h_convt2_tail for all K (= 4) mask tokens of the three-mask heads (inference; mask_decoder.py:227-234):
+ * hyper [B, K, 32], masks [B, K, 2H * 2W]; the activation of a pixel is computed once and feeds the K
+ * products, each summed in s2h_convt2_tail's order (masks[:, 0] equals its output bit for bit).
+ * pre / post may be NULL (forward only). */
+int s2h_convt2_tail_k(int dt, int B, int H, int W, int Co, int K, const void* Y, const float* bias, const void* add,
+                      int add_bcast, const void* hyper, void* pre, void* post, void* masks, hipStream_t st);
+/* Stability counts of mask logits (mask_decoder.py:247-257): counts[2b] = #{p: m[b][p] > delta},
+ * counts[2b + 1] = #{p: m[b][p] > -delta} over p < P of row b (row stride ld elements), compared on the
+ * stored value widened to fp32; integer sums in a fixed order.  bf16 or fp32. */
+int s2h_stability_counts(int dt, int B, int64_t P, const void* masks, int64_t ld, float delta, int* counts,
+                         hipStream_t st);
+/* Per-object output selection of the three-mask heads (mask_decoder.py:145-166, 259-295 and
+ * sam2_base.py:380-420).  masks [B, K, P] (dt), iou [B, K] fp32, score [B] fp32, tok: the K mask tokens
+ * of object b at tok + b * ld_tok, each [C] (dt).  best = 1 + first argmax(iou[b][1:K]).
+ * mode 0 (multimask): idx = best; mode 1 (dynamic single): idx = 0 when
+ * (counts[2b+1] > 0 ? counts[2b] / counts[2b+1] : 1) >= thresh in fp32, else best.
+ * Writes idx [B] int32, low [B, P] fp32 = masks[b][idx] where score[b] > 0 else fill, iou_out [B] =
+ * iou[b][idx], tok_out [B, C] = token idx when mode 0 and tok_follow, else token 0, and, when not NULL,
+ * multi_low [B, K-1, P] fp32 = the gated candidates 1..K-1. */
+int s2h_multimask_select(int dt, int B, int K, int64_t P, int C, const void* masks, const float* iou,
+                         const int* counts, const float* score, const void* tok, int64_t ld_tok, int mode,
+                         int tok_follow, float thresh, float fill, int* idx, float* low, float* iou_out,
+                         void* tok_out, float* multi_low, hipStream_t st);
 /* The first upscaling step in one pass (mask_decoder.py:105-106, bf16, Co = 64): pre = the s2h_convt2_store
  * values, y / mean / rstd = LayerNorm2d(pre) over the channels (gamma, beta, eps; the values of
  * s2h_layernorm_fwd), post = gelu(y) (as s2h_act_fwd rounds it); mean / rstd [B * 2H * 2W] fp32. */

@@ -11,7 +11,7 @@
 
 namespace {
 
-constexpr int HD_MAXH = 4;    // heads per launch
+constexpr int HD_MAXH = 8;    // heads per launch (the multimask decoder: 4 hypernetworks + IoU + object score)
 constexpr int HD_MAXL = 3;    // layers per head
 constexpr int HD_MAXK = 256;  // widest layer input / output
 constexpr int HD_LD = HD_MAXK + 8;  // LDS activation row (bf16), padded: conflict-free b128 reads

@@ -226,7 +226,7 @@ def _head_ok(m, x):
 
 def _heads_fusable(pairs):
     import os
-    return (0 < len(pairs) <= 4 and os.environ.get("S2H_MLP_HEADS", "1") != "0"
+    return (0 < len(pairs) <= 8 and os.environ.get("S2H_MLP_HEADS", "1") != "0"
             and len({x.shape[0] for _, x in pairs}) == 1 and all(_head_ok(m, x) for m, x in pairs))
 
 

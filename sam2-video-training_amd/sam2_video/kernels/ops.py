@@ -1138,6 +1138,69 @@ def convt2_tail_enabled():
     return os.environ.get("S2H_CONVT_TAIL", "1") == "1"
 
 
+def convt2_tail_k(Y, B, H, W, Co, bias, add, hyper, masks=None, pre=None, post=None):
+    """masks[b, k] = gelu(convt2_store(Y) + bias + add)[b] . hyper[b, k] for the K = 4 mask tokens in one
+    pass (s2h_convt2_tail_k; bf16, Co = 32); masks [B, K, 2H * 2W]; pre / post optional outputs"""
+    K = hyper.shape[1]
+    bc = 0
+    if add is not None:
+        assert add.is_contiguous() and add.dtype == Y.dtype and add.shape[0] in (1, B)
+        assert add.numel() == add.shape[0] * 4 * H * W * Co
+        bc = int(add.shape[0] == 1 and B > 1)
+    assert Y.is_contiguous() and Y.numel() == B * H * W * 4 * Co
+    assert hyper.is_contiguous() and hyper.dtype == Y.dtype and hyper.shape == (B, K, Co)
+    if masks is None:
+        masks = torch.empty(B, K, 4 * H * W, device=Y.device, dtype=Y.dtype)
+    assert masks.is_contiguous() and masks.dtype == Y.dtype and masks.numel() == B * K * 4 * H * W
+    for t in (pre, post):
+        assert t is None or (t.is_contiguous() and t.dtype == Y.dtype and t.numel() == B * 4 * H * W * Co)
+    _dev(Y, hyper, masks)
+    call("s2h_convt2_tail_k", dt(Y), B, H, W, Co, K, ptr(Y), ptr(bias), ptr(add), bc, ptr(hyper), ptr(pre), ptr(post),
+         ptr(masks), stream())
+    return masks
+
+
+def stability_counts(masks, delta, counts=None):
+    """masks [B, P] (bf16 / fp32 rows, unit inner stride) -> int32 [B, 2]: per row the number of logits
+    > delta and > -delta (s2h_stability_counts; the stability score's two areas, mask_decoder.py:247-257)"""
+    B, P = masks.shape
+    assert masks.stride(1) == 1 and (B == 1 or masks.stride(0) >= P)
+    if counts is None:
+        counts = torch.empty(B, 2, device=masks.device, dtype=torch.int32)
+    assert counts.is_contiguous() and counts.dtype == torch.int32 and counts.shape == (B, 2)
+    _dev(masks, counts)
+    call("s2h_stability_counts", dt(masks), B, P, ptr(masks), masks.stride(0) if B > 1 else P, float(delta),
+         ptr(counts), stream())
+    return counts
+
+
+def multimask_select(masks, iou, score, tokens, *, dynamic=False, counts=None, thresh=0.0, token_follows=False,
+                     fill=0.0, want_candidates=False):
+    """Output selection of the three-mask heads (s2h_multimask_select).  masks [B, K, P], iou [B, K] fp32,
+    score [B] fp32, tokens [B, K, C] (rows of a larger token array allowed: unit inner strides).
+    -> (idx int32 [B], low fp32 [B, P] gated by score > 0 else `fill`, iou fp32 [B], token [B, C],
+    gated candidates 1..K-1 fp32 [B, K-1, P] or None)"""
+    B, K, P = masks.shape
+    C = tokens.shape[2]
+    assert masks.is_contiguous() and tokens.dtype == masks.dtype and tokens.shape[:2] == (B, K)
+    assert tokens.stride(2) == 1 and tokens.stride(1) == C and (B == 1 or tokens.stride(0) >= K * C)
+    assert iou.is_contiguous() and iou.dtype == torch.float32 and iou.shape == (B, K)
+    assert score.is_contiguous() and score.dtype == torch.float32 and score.numel() == B
+    if dynamic:
+        assert counts is not None and counts.is_contiguous() and counts.dtype == torch.int32 and counts.shape == (B, 2)
+    dev = masks.device
+    idx = torch.empty(B, device=dev, dtype=torch.int32)
+    low = torch.empty(B, P, device=dev, dtype=torch.float32)
+    iou_out = torch.empty(B, device=dev, dtype=torch.float32)
+    tok_out = torch.empty(B, C, device=dev, dtype=masks.dtype)
+    multi = torch.empty(B, K - 1, P, device=dev, dtype=torch.float32) if want_candidates else None
+    _dev(masks, iou, score, tokens)
+    call("s2h_multimask_select", dt(masks), B, K, P, C, ptr(masks), ptr(iou), ptr(counts) if dynamic else None,
+         ptr(score), ptr(tokens), tokens.stride(0) if B > 1 else K * C, int(bool(dynamic)), int(bool(token_follows)),
+         float(thresh), float(fill), ptr(idx), ptr(low), ptr(iou_out), ptr(tok_out), ptr(multi), stream())
+    return idx, low, iou_out, tok_out, multi
+
+
 def convt2_gather(dout, B, H, W, Co, dY=None):
     if dY is None:
         dY = torch.empty(B * H * W, 4 * Co, device=dout.device, dtype=dout.dtype)

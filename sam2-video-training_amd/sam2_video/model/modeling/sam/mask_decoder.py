@@ -68,6 +68,11 @@ class MaskDecoder(nn.Module):
         self.pred_obj_scores = pred_obj_scores
         self.obj_score_token = Embedding(1, transformer_dim)
         self.use_multimask_token_for_obj_ptr = use_multimask_token_for_obj_ptr
+        # single-mask output falls back to the best multimask token when token 0's mask is unstable
+        # (inference only, mask_decoder.py:104-108,149-150)
+        self.dynamic_multimask_via_stability = bool(dynamic_multimask_via_stability)
+        self.dynamic_multimask_stability_delta = float(dynamic_multimask_stability_delta)
+        self.dynamic_multimask_stability_thresh = float(dynamic_multimask_stability_thresh)
         self.output_upscaling = nn.Sequential(
             ConvTranspose2x2(transformer_dim, transformer_dim // 4), LayerNorm2d(transformer_dim // 4), Identity(),
             ConvTranspose2x2(transformer_dim // 4, transformer_dim // 8), Identity())
@@ -125,3 +130,50 @@ class MaskDecoder(nn.Module):
             score = self.pred_obj_score_head(hs[:, 0].detach().contiguous())
             score = ops.cast(score, torch.float32) if score.dtype != torch.float32 else score
         return masks, iou0, mask_token0, score
+
+    @torch.no_grad()
+    def forward_multimask(self, image_embeddings, h, w, image_pe_table, sparse, no_mask_embed, high_res_features,
+                          dense=None):
+        """Inference-only forward that evaluates every mask token (mask_decoder.py:227-245): the inputs of
+        `forward` -> (mask logits of the K = 4 tokens [O, K, 4h*4w] compute dtype, IoU predictions [O, K]
+        f32, the K mask tokens [O, K, C] (rows of the transformer output), object score logits [O, 1]
+        f32).  The caller selects (ops.multimask_select).  The K hypernetwork MLPs, the IoU head and the
+        object-score head are one launch; in bf16 the last upscaling step, GELU and the K hypernetwork
+        products are one pass over the GEMM output (ops.convt2_tail_k), the activation read once."""
+        O = image_embeddings.shape[0]
+        C = self.transformer_dim
+        K = self.num_mask_tokens
+        dt = image_embeddings.dtype
+        tokens = _DecoderTokens.apply(sparse, dt, self.obj_score_token.weight, self.iou_token.weight,
+                                      self.mask_tokens.weight)
+        if dense is None:
+            src = FN.add_bcast(image_embeddings, no_mask_embed.weight._s2h_compute.view(-1), bparam=no_mask_embed.weight)
+        else:
+            src = FN.add(image_embeddings, dense)
+        hs, src = self.transformer(src, image_pe_table, tokens)
+        hs = hs.contiguous()
+        feat_s0, feat_s1 = high_res_features
+        dc1, ln1, _, dc2, _ = self.output_upscaling
+        u = conv_transpose2x2(src.view(O, h, w, C), dc1, add=feat_s1)
+        u = FN.act(ln1(u), "gelu")
+        heads = list(self.output_hypernetworks_mlps) + [self.iou_prediction_head, self.pred_obj_score_head]
+        rows = [hs[:, 2 + k] for k in range(K)] + [hs[:, 1], hs[:, 0]]
+        pairs = list(zip(heads, rows))
+        if not FN._heads_fusable(pairs):  # fp32 parity mode: each head's own GEMMs, on contiguous rows
+            pairs = [(m, x.contiguous()) for m, x in pairs]
+        outs = FN.mlp_heads_nograd(pairs)
+        hyper = torch.stack(list(outs[:K]), dim=1).contiguous()  # [O, K, C / 8]
+        f32 = lambda x: x if x.dtype == torch.float32 else ops.cast(x.contiguous(), torch.float32)  # noqa: E731
+        iou, score = f32(outs[K]).contiguous(), f32(outs[K + 1]).contiguous()
+        Co = dc2.out_ch
+        B, H, W, Ci = u.shape
+        if dt == torch.bfloat16 and Co == 32 and K == 4:
+            Y = torch.empty(B * H * W, 4 * Co, device=u.device, dtype=dt)
+            ops.gemm(u.reshape(-1, Ci), dc2.compute_weight(), Y, M=B * H * W, N=4 * Co, K=Ci, lda_m=Ci, lda_k=1,
+                     ldb_k=4 * Co, ldb_n=1, ldc=4 * Co)
+            masks = ops.convt2_tail_k(Y, B, H, W, Co, dc2.bias.detach(), feat_s0.contiguous(), hyper)
+        else:  # fp32 parity mode: the existing upscaling kernels and one batched GEMM with K rows
+            u = FN.act(conv_transpose2x2(u, dc2, add=feat_s0), "gelu")
+            masks = torch.empty(O, K, 4 * H * W, device=u.device, dtype=dt)
+            ops.bmm(hyper, u.view(O, 4 * H * W, Co), masks, trans_b=True)
+        return masks, iou, hs[:, 2:2 + K], score

@@ -10,7 +10,10 @@ Supported configuration: the SAM2.1 training setup of the reference YAML
 (configs/sam2/sam2.1_hiera_t.yaml:87-121) -- high-res features, object pointers
 with signed projected temporal encodings, object scores with fixed no-object
 pointer, no-object spatial embedding, directly added no-memory embedding,
-single-mask output.  Other flag values raise.
+single-mask output.  Other flag values raise.  The three-mask SAM heads of upstream's
+released configs (`multimask_output_in_sam` and the flags that go with it, the
+stability fallback of the single-mask output) are built for inference only: a
+training forward with them raises (the reference's loss is undefined for K = 3).
 """
 from __future__ import annotations
 
@@ -114,7 +117,7 @@ class SAM2Base(nn.Module):
         ok = (self.use_high_res_features_in_sam and self.use_obj_ptrs_in_encoder and self.pred_obj_scores
               and self.fixed_no_obj_ptr and not self.soft_no_obj_ptr and self.proj_tpos_enc_in_obj_ptrs
               and self.add_tpos_enc_to_obj_ptrs and self.directly_add_no_mem_embed
-              and not self.multimask_output_in_sam and self.mem_dim < self.hidden_dim and self.num_maskmem > 0)
+              and self.mem_dim < self.hidden_dim and self.num_maskmem > 0)
         if not ok:
             raise NotImplementedError("this build implements the SAM2.1 training configuration "
                                       "(configs/sam2/sam2.1_hiera_t.yaml flags)")
@@ -122,6 +125,22 @@ class SAM2Base(nn.Module):
     @property
     def device(self):
         return next(self.parameters()).device
+
+    MULTIMASK_TRAINING_MSG = ("multimask SAM heads (multimask_output_in_sam=True) are built for inference only: "
+                              "the reference's training loss is undefined for three candidate masks "
+                              "(losses.py:149-171); call model.eval() or build the model without the multimask flags")
+
+    def _refuse_multimask_training(self):
+        if self.training and self.multimask_output_in_sam:
+            raise NotImplementedError(self.MULTIMASK_TRAINING_MSG)
+
+    def _use_multimask(self, is_init_cond_frame, point_inputs):
+        """whether the SAM heads output three candidate masks (sam2_base.py:932-940); a box counts as
+        two points, a tracked frame without prompts has none"""
+        num_pts = 0 if point_inputs is None else point_inputs["point_labels"].size(1)
+        return bool(self.multimask_output_in_sam
+                    and (is_init_cond_frame or self.multimask_output_for_tracking)
+                    and (self.multimask_min_pt_num <= num_pts <= self.multimask_max_pt_num))
 
     def _build_sam_heads(self):
         """sam2_base.py:212-260"""
@@ -278,11 +297,19 @@ class SAM2Base(nn.Module):
         return self.memory_attention(feat, pos, memory, mpos, num_obj_ptr_tokens=n_ptr_tok, num_objects=num_objects)
 
     # ------------------------------------------------------------ heads
-    def _forward_sam_heads(self, pix, prompt, high_res, num_objects, dense=None):
-        """sam2_base.py:262-434 (single mask).  pix [O, L, C]; prompt (pe [O, N, C] f32, labels [O, N]
+    def _forward_sam_heads(self, pix, prompt, high_res, num_objects, dense=None, multimask_output=False,
+                           extras=None):
+        """sam2_base.py:262-434.  pix [O, L, C]; prompt (pe [O, N, C] f32, labels [O, N]
         int32) on the device; high_res (s0, s1) NHWC (batch 1 = broadcast over objects); `dense` an
         optional mask-prompt embedding [O, L, C] (prompt_encoder._embed_masks, the predictor's
-        refinement clicks) in place of no_mask_embed."""
+        refinement clicks) in place of no_mask_embed.  `multimask_output` (or, in eval mode, the
+        decoder's dynamic_multimask_via_stability) takes the inference-only three-mask path
+        (_forward_sam_heads_multimask); `extras`, a dict, then receives its candidates."""
+        if multimask_output or (self.sam_mask_decoder.dynamic_multimask_via_stability and not self.training):
+            if self.training or torch.is_grad_enabled():
+                raise NotImplementedError(self.MULTIMASK_TRAINING_MSG + " (and run it under torch.no_grad())")
+            return self._forward_sam_heads_multimask(pix, prompt, high_res, num_objects, dense, multimask_output,
+                                                     extras)
         O = num_objects
         h = w = self.sam_image_embedding_size
         dt = pix.dtype
@@ -309,6 +336,54 @@ class SAM2Base(nn.Module):
                 ptr = self.obj_ptr_proj(token0.detach())
             ptr = ops.gate_mix(ptr, score_flat, self.no_obj_ptr._s2h_compute.view(-1), scale_x=self.fixed_no_obj_ptr)
         return low, high, ious, ptr, score
+
+    @torch.no_grad()
+    def _forward_sam_heads_multimask(self, pix, prompt, high_res, num_objects, dense, multimask_output, extras=None):
+        """The three-mask SAM heads (inference; mask_decoder.py:145-166,259-295, sam2_base.py:380-428).
+        multimask_output: the candidate 1..3 of highest predicted IoU is the output and (with
+        use_multimask_token_for_obj_ptr) its token the object pointer; otherwise the decoder's dynamic
+        stability rule: token 0 while its stability score >= thresh, else that best candidate (the
+        pointer stays token 0).  Only the chosen mask is upsampled.  Returns the tuple of
+        _forward_sam_heads (ious [O, 1] = the chosen IoU prediction); `extras` receives best_idx int32
+        [O], all_masks [O, 4, P] (ungated, compute dtype), all_ious [O, 4] f32, and on the multimask
+        path low_res_multimasks f32 [O, 3, 4h, 4w] (gated) / ious [O, 3] as the reference returns them
+        (high_res_multimasks too when extras asks with {"high_res_multimasks": True}), on the dynamic
+        path stability_counts int32 [O, 2]."""
+        O = num_objects
+        h = w = self.sam_image_embedding_size
+        dt = pix.dtype
+        dec = self.sam_mask_decoder
+        pe_dev, lab_dev = prompt
+        sparse = self.sam_prompt_encoder.sparse(pe_dev, lab_dev, dt)
+        dense_pe = self.sam_prompt_encoder.dense_pe_table(pix.device, dt)
+        masks, ious, tokens, score = dec.forward_multimask(pix, h, w, dense_pe, sparse,
+                                                           self.sam_prompt_encoder.no_mask_embed, high_res,
+                                                           **({"dense": dense} if dense is not None else {}))
+        score_flat = score.view(-1).contiguous()
+        counts = None
+        if not multimask_output:
+            counts = ops.stability_counts(masks[:, 0], dec.dynamic_multimask_stability_delta)
+        idx, low, iou, token, multi = ops.multimask_select(
+            masks, ious, score_flat, tokens, dynamic=not multimask_output, counts=counts,
+            thresh=dec.dynamic_multimask_stability_thresh, token_follows=dec.use_multimask_token_for_obj_ptr,
+            fill=NO_OBJ_SCORE, want_candidates=multimask_output)
+        low = low.view(O, 4 * h, 4 * w)
+        high = FN.bilinear(low, self.image_size, self.image_size)
+        ptr = FN.mlp_heads_nograd([(self.obj_ptr_proj, token)])[0] if hasattr(self.obj_ptr_proj, "layers") \
+            else self.obj_ptr_proj(token)
+        ptr = ops.gate_mix(ptr, score_flat, self.no_obj_ptr._s2h_compute.view(-1), scale_x=self.fixed_no_obj_ptr)
+        if extras is not None:
+            want_high = bool(extras.get("high_res_multimasks"))
+            extras.update(best_idx=idx, all_masks=masks, all_ious=ious)
+            if multimask_output:
+                extras.update(low_res_multimasks=multi.view(O, -1, 4 * h, 4 * w), ious=ious[:, 1:])
+                if want_high:
+                    K1 = multi.shape[1]
+                    hi = FN.bilinear(multi.view(O * K1, 4 * h, 4 * w), self.image_size, self.image_size)
+                    extras["high_res_multimasks"] = hi.view(O, K1, self.image_size, self.image_size)
+            else:
+                extras.update(stability_counts=counts)
+        return low, high, iou.view(O, 1), ptr, score
 
     @torch.no_grad()
     def _use_mask_as_output(self, feat, masks, score, high_res, num_objects):

@@ -36,13 +36,25 @@ DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp32": torch.floa
           "fp8": torch.bfloat16, "mxfp8": torch.bfloat16}
 
 
+def merge_model_overrides(cfg: Dict[str, Any], overrides: Optional[Dict[str, Any]]) -> Dict[str, Any]:
+    """top-level model flags of `overrides` over the loaded config (a copy); `sam_mask_decoder_extra_args`
+    is merged one level deep, so an override of one decoder argument keeps the config's others"""
+    out = dict(cfg)
+    for k, v in (overrides or {}).items():
+        if k == "sam_mask_decoder_extra_args" and v is not None:
+            out[k] = {**(out.get(k) or {}), **v}
+        else:
+            out[k] = v
+    return out
+
+
 class SAM2Model(SAM2Base):
     def __init__(self, checkpoint_path: Optional[str], config_path: str, fintuned_model_path: Optional[str] = None,
                  trainable_modules: Optional[List[str]] = None, device: str = "cuda", prompt_type: str = "point",
                  forward_backbone_per_frame_for_eval: bool = False, num_pos_points: int = 1,
                  num_neg_points: int = 0, include_center: bool = True, use_activation_checkpoint: bool = False,
                  random_init_memory_modules: bool = False, compute_dtype="bf16", image_size: Optional[int] = None,
-                 init_seed: int = 0):
+                 init_seed: int = 0, model_overrides: Optional[Dict[str, Any]] = None):
         self.checkpoint_path = checkpoint_path
         self.config_path = config_path
         self.prompt_type = prompt_type
@@ -52,7 +64,7 @@ class SAM2Model(SAM2Base):
         self.num_neg_points = num_neg_points
         self.include_center = include_center
         self.fintuned_model_path = fintuned_model_path
-        cfg = load_model_config(config_path, image_size)
+        cfg = merge_model_overrides(load_model_config(config_path, image_size), model_overrides)
         kw = {k: instantiate(v) for k, v in cfg.items() if k != "_target_"}
         super().__init__(use_activation_checkpoint=use_activation_checkpoint, **kw)
         if prompt_type == "mask" and not self.use_mask_input_as_output_without_sam:
@@ -280,6 +292,7 @@ class SAM2Model(SAM2Base):
     # ------------------------------------------------------------- forward
     def forward(self, input: BatchedVideoDatapoint) -> Tuple[List[Dict[str, Any]], List[int]]:
         """sam2model.py:153-179"""
+        self._refuse_multimask_training()
         if self.arena is None:
             raise RuntimeError("call SAM2Model.load(device) before forward")
         if self.fp8:
@@ -381,6 +394,7 @@ class SAM2Model(SAM2Base):
     def forward_tracking(self, backbone_out, input: BatchedVideoDatapoint, return_dict=False):
         """sam2model.py:266-401 -- sequential frames, detached memory bank pruned to the
         last num_maskmem-1 non-conditioning frames."""
+        self._refuse_multimask_training()
         fpn = backbone_out["backbone_fpn"]
         T = backbone_out["num_frames"]
         h = w = self.sam_image_embedding_size
@@ -427,7 +441,9 @@ class SAM2Model(SAM2Base):
             else:
                 pix = self._prepare_memory_conditioned_features(t, is_cond, feat_t, pos, T, output_dict, O)
                 prompt = backbone_out["prompt_cond"] if is_cond else backbone_out["prompt_pad"]
-                low, high, ious, ptr, score = self._forward_sam_heads(pix, prompt, (s0_t, s1_t), O)
+                mm = self._use_multimask(is_cond, backbone_out["point_inputs_per_frame"].get(t))
+                low, high, ious, ptr, score = self._forward_sam_heads(pix, prompt, (s0_t, s1_t), O,
+                                                                      **({"multimask_output": True} if mm else {}))
             mfeat, mpos = self._encode_new_memory(feat_t, high, score, O)
             entry = {"maskmem_features": mfeat, "maskmem_pos_enc": mpos, "obj_ptr": ptr}
             if is_cond:

@@ -112,6 +112,8 @@ class SAM2VideoPredictor:
         self.binarize_mask_from_pts_for_mem_enc = binarize_mask_from_pts_for_mem_enc
         self.maskmem_storage_dtype = maskmem_storage_dtype
         self.frame_chunk = max(1, int(frame_chunk))
+        # keep every mask token's low-res logits of the three-mask heads in the frame outputs
+        self.keep_multimask_candidates = False
         model.eval()
 
     def __getattr__(self, name):
@@ -341,6 +343,7 @@ class SAM2VideoPredictor:
         h = m.sam_image_embedding_size
         dev = s["device"]
         pe1, lab1 = self._pad_prompt(s, O)
+        extras = None
         if mask_inputs is not None:
             mk = mask_inputs.reshape(O, m.image_size, m.image_size).to(dev)
             score = ((mask_inputs.reshape(O, -1).amax(dim=1) > 0).float() * 20.0 - 10.0).to(dev)
@@ -363,7 +366,18 @@ class SAM2VideoPredictor:
             if prev_sam_mask_logits is not None:
                 dense = m.sam_prompt_encoder.dense_from_mask(
                     prev_sam_mask_logits.reshape(O, 4 * h, 4 * h, 1).contiguous(), m.compute_dtype)
-            low, high, _, ptr, score = m._forward_sam_heads(pix, prompt, (s0, s1), O, dense=dense)
+            # three candidate masks for a single click / a tracked frame when the config asks for them
+            # (upstream track_step; a box counts as two points, a tracked frame has none)
+            if m._use_multimask(is_init_cond_frame, point_inputs):
+                extras = {}
+                low, high, ious, ptr, score = m._forward_sam_heads(pix, prompt, (s0, s1), O, dense=dense,
+                                                                   multimask_output=True, extras=extras)
+            elif m.sam_mask_decoder.dynamic_multimask_via_stability:
+                extras = {}
+                low, high, ious, ptr, score = m._forward_sam_heads(pix, prompt, (s0, s1), O, dense=dense,
+                                                                   extras=extras)
+            else:
+                low, high, _, ptr, score = m._forward_sam_heads(pix, prompt, (s0, s1), O, dense=dense)
         low = low.view(O, 1, 4 * h, 4 * h)
         mfeat = mpos = None
         if run_mem_encoder:
@@ -375,6 +389,13 @@ class SAM2VideoPredictor:
             outs.append({"maskmem_features": None if mfeat is None else mfeat[i:i + 1],
                          "maskmem_pos_enc": mpos, "pred_masks": low[i:i + 1], "obj_ptr": ptr[i:i + 1],
                          "object_score_logits": score.reshape(O, 1)[i:i + 1]})
+            if extras is not None:  # the three-mask heads' selection (absent on the single-mask path)
+                outs[-1]["best_mask_idx"] = extras["best_idx"][i:i + 1]
+                outs[-1]["all_ious"] = extras["all_ious"][i:i + 1]
+                if self.keep_multimask_candidates:  # [1, 4, P] ungated, compute dtype (diagnostics / tests)
+                    outs[-1]["all_low_res_masks"] = extras["all_masks"][i:i + 1]
+                if "stability_counts" in extras:
+                    outs[-1]["stability_counts"] = extras["stability_counts"][i:i + 1]
         return outs
 
     def _pad_prompt(self, s, O):
@@ -519,15 +540,32 @@ class SAM2VideoPredictor:
         return list(ids), [(t, self._video_res(s, self._consolidate(s, t, is_cond=True))) for t in frames]
 
 
+# what upstream's released SAM2 / SAM2.1 model configs set and what upstream's build_sam2_video_predictor
+# adds to them (`sam_mask_decoder_extra_args`): the three-mask SAM heads and the stability fallback
+UPSTREAM_MULTIMASK_OVERRIDES = {
+    "multimask_output_in_sam": True, "multimask_output_for_tracking": True, "use_multimask_token_for_obj_ptr": True,
+    "multimask_min_pt_num": 0, "multimask_max_pt_num": 1,
+    "sam_mask_decoder_extra_args": {"dynamic_multimask_via_stability": True,
+                                    "dynamic_multimask_stability_delta": 0.05,
+                                    "dynamic_multimask_stability_thresh": 0.98},
+}
+
+
 def build_sam2_video_predictor(config_file, ckpt_path=None, device="cuda", mode="eval", hydra_overrides_extra=(),
                                apply_postprocessing=True, vos_optimized=False, compute_dtype="bf16", image_size=None,
-                               **kwargs):
+                               multimask: bool = False, **kwargs):
     """upstream sam2.build_sam.build_sam2_video_predictor: the SAM2.1 model of `config_file`
     (named sizes, upstream config names or a YAML path, model/build.py) with `ckpt_path`
     weights (deterministic synthetic weights when absent, as everywhere offline), as a
     predictor with upstream's post-processing (binarised user masks into memory, hole filling
-    of area <= 8)."""
-    from .model.sam2model import SAM2Model
+    of area <= 8).  `multimask=True` applies UPSTREAM_MULTIMASK_OVERRIDES -- what upstream's released
+    configs and builder do: three candidate masks on a single click and on tracked frames (the one of
+    highest predicted IoU wins and its token is the object pointer), the stability fallback on box /
+    multi-click prompts.  The default keeps the single-mask heads of the training configuration."""
+    from .model.sam2model import SAM2Model, merge_model_overrides
+    if multimask:
+        kwargs["model_overrides"] = merge_model_overrides(UPSTREAM_MULTIMASK_OVERRIDES,
+                                                          kwargs.get("model_overrides"))
     model = SAM2Model(ckpt_path, config_file, trainable_modules=[], compute_dtype=compute_dtype,
                       image_size=image_size, **kwargs)
     model.load(device)
