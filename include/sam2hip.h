@@ -608,6 +608,21 @@ int s2h_multimask_select(int dt, int B, int K, int64_t P, int C, const void* mas
                          const int* counts, const float* score, const void* tok, int64_t ld_tok, int mode,
                          int tok_follow, float thresh, float fill, int* idx, float* low, float* iou_out,
                          void* tok_out, float* multi_low, hipStream_t st);
+/* 8-connected components of N independent H x W images (upstream sam2/utils/misc.py
+ * get_connected_components).  Foreground is scores > 0 when `positive`, scores <= 0 otherwise.
+ * labels[p] = 0 off the foreground, else 1 + the smallest row-major index (within its image) of a pixel of
+ * p's component; areas[p] = the pixel count of p's component, 0 off the foreground.  Both int32 [N, H, W].
+ * A pure function of the input (integer atomics with a unique fixed point, no float atomics), no host
+ * round trip, every device loop bounded by 2 H W + 2 steps.  H, W >= 1, H * W <= 2^24,
+ * N * H * W < 2^31 - 256. */
+int s2h_cc_label(int N, int H, int W, const float* scores, int positive, int* labels, int* areas,
+                 hipStream_t st);
+/* upstream fill_holes_in_mask_scores on fp32 scores [N, H, W]: first the background components
+ * (scores <= 0) of area <= max_area become 0.1f, then, on that result, the foreground components (> 0) of
+ * area <= max_area become -0.1f; every other element is copied bit for bit.  work: 2 N H W int32 of
+ * scratch; out must not alias scores; max_area >= 1; sizes as for s2h_cc_label. */
+int s2h_fill_holes(int N, int H, int W, const float* scores, int max_area, float* out, int* work,
+                   hipStream_t st);
 /* The first upscaling step in one pass (mask_decoder.py:105-106, bf16, Co = 64): pre = the s2h_convt2_store
  * values, y / mean / rstd = LayerNorm2d(pre) over the channels (gamma, beta, eps; the values of
  * s2h_layernorm_fwd), post = gelu(y) (as s2h_act_fwd rounds it); mean / rstd [B * 2H * 2W] fp32. */

@@ -1201,6 +1201,38 @@ def multimask_select(masks, iou, score, tokens, *, dynamic=False, counts=None, t
     return idx, low, iou_out, tok_out, multi
 
 
+def cc_label(scores, positive=True):
+    """8-connected components of N images (s2h_cc_label).  scores [N, H, W] fp32 contiguous; foreground is
+    scores > 0 (`positive`) or scores <= 0.  -> (labels, areas) int32 [N, H, W]: 0 off the foreground, else
+    1 + the smallest in-image index of the pixel's component, and the component's pixel count."""
+    assert scores.dim() == 3 and scores.dtype == torch.float32 and scores.is_contiguous()
+    _dev(scores)
+    N, H, W = scores.shape
+    labels = torch.empty(N, H, W, device=scores.device, dtype=torch.int32)
+    areas = torch.empty(N, H, W, device=scores.device, dtype=torch.int32)
+    call("s2h_cc_label", N, H, W, ptr(scores), int(bool(positive)), ptr(labels), ptr(areas), stream())
+    return labels, areas
+
+
+def fill_holes(scores, max_area, out=None):
+    """upstream fill_holes_in_mask_scores (s2h_fill_holes): background components of area <= max_area become
+    0.1, then foreground components of area <= max_area of that result become -0.1; the rest is copied.
+    scores [N, H, W] or [N, 1, H, W] fp32 contiguous -> the same shape.  The scratch (2 int32 per pixel)
+    comes from the torch allocator, so the call can be captured in a HIP graph."""
+    assert scores.dim() in (3, 4) and scores.dtype == torch.float32 and scores.is_contiguous()
+    assert scores.dim() == 3 or scores.shape[1] == 1
+    assert int(max_area) > 0, "max_area must be positive"
+    if out is None:
+        out = torch.empty_like(scores)
+    assert out.shape == scores.shape and out.dtype == torch.float32 and out.is_contiguous()
+    assert out.data_ptr() != scores.data_ptr() or scores.numel() == 0, "fill_holes does not run in place"
+    _dev(scores, out)
+    N, H, W = scores.shape[0], scores.shape[-2], scores.shape[-1]
+    work = torch.empty(2 * N * H * W, device=scores.device, dtype=torch.int32)
+    call("s2h_fill_holes", N, H, W, ptr(scores), int(max_area), ptr(out), ptr(work), stream())
+    return out
+
+
 def convt2_gather(dout, B, H, W, Co, dY=None):
     if dY is None:
         dY = torch.empty(B * H * W, 4 * Co, device=dout.device, dtype=dout.dtype)

@@ -18,7 +18,9 @@ published SAM2.1 algorithm (sam2/sam2_video_predictor.py):
     conditioning frames return their stored output, every other frame runs memory attention +
     SAM heads + memory encoder; the memory bank keeps every frame (selection by distance);
   * memory features are stored in bf16 (as upstream stores them), low-res mask logits in fp32;
-  * optional hole filling of the low-res logits (`fill_hole_area`, 8 in build_sam2_video_predictor).
+  * optional hole filling of the low-res logits (`fill_hole_area`, 8 in build_sam2_video_predictor):
+    connected components and the fill are HIP kernels (csrc/cc.hip), stream-ordered between the SAM
+    heads and the bilinear upsampling; `postprocess_on_device=False` keeps the host scipy path for A/B.
 
 MI355X-first choices (not observable in the outputs): objects whose conditioning / tracked frame
 sets agree are run as ONE batch through the kernels instead of one object at a time (each object
@@ -72,19 +74,41 @@ def _load_frames(video_path, image_size):
 
 
 def _connected_components(binary):
-    """8-connected components -> (labels, per-pixel component area); host scipy on the low-res
-    mask (upstream's get_connected_components contract)"""
+    """8-connected components -> (labels, per-pixel component area); host scipy (the CPU path of
+    fill_holes_in_mask_scores; GPU tensors take get_connected_components / ops.fill_holes)"""
     from scipy import ndimage
     lab, n = ndimage.label(binary, structure=np.ones((3, 3), dtype=np.int32))
     areas = np.bincount(lab.ravel(), minlength=n + 1)
     return lab, areas[lab]
 
 
+def get_connected_components(mask: torch.Tensor):
+    """upstream sam2/utils/misc.py get_connected_components: mask [N, 1, H, W] bool / uint8 on the GPU
+    (non-zero = foreground) -> (labels, counts), both int32 [N, 1, H, W]: the 8-connected component of
+    every foreground pixel (1 + the smallest row-major index of the component within its image, so the
+    result does not depend on scheduling) and that component's area; 0 on the background.  HIP kernels
+    (csrc/cc.hip), no host round trip."""
+    assert mask.dim() == 4 and mask.shape[1] == 1, "mask must be [N, 1, H, W]"
+    if not mask.is_cuda:
+        raise RuntimeError("get_connected_components runs on the GPU only (as upstream's kernel)")
+    N, _, H, W = mask.shape
+    labels, counts = ops.cc_label(mask.reshape(N, H, W).to(torch.float32).contiguous(), positive=True)
+    return labels.view(N, 1, H, W), counts.view(N, 1, H, W)
+
+
 def fill_holes_in_mask_scores(mask: torch.Tensor, max_area: int) -> torch.Tensor:
     """upstream sam2/utils/misc.py fill_holes_in_mask_scores: background components (score <= 0)
     of area <= max_area become 0.1, then foreground sprinkles (score > 0) of area <= max_area
-    become -0.1.  mask [N, 1, h, w] fp32."""
+    become -0.1.  mask [N, 1, h, w] fp32.  A GPU tensor stays on the device (ops.fill_holes); a CPU
+    tensor takes host scipy -- the oracle of the kernels' tests."""
     assert max_area > 0, "max_area must be positive"
+    if mask.is_cuda:
+        return ops.fill_holes(mask.detach().float().contiguous(), max_area)
+    return _fill_holes_host(mask, max_area)
+
+
+def _fill_holes_host(mask: torch.Tensor, max_area: int) -> torch.Tensor:
+    """the host path: copy to the host, scipy per object, copy back"""
     m = mask.detach().float().cpu().numpy()
     for i in range(m.shape[0]):
         lab, area = _connected_components(m[i, 0] <= 0)
@@ -101,7 +125,7 @@ class SAM2VideoPredictor:
     def __init__(self, model, fill_hole_area: int = 0, non_overlap_masks: bool = False,
                  clear_non_cond_mem_around_input: bool = False, add_all_frames_to_correct_as_cond: bool = False,
                  binarize_mask_from_pts_for_mem_enc: bool = True, maskmem_storage_dtype=torch.bfloat16,
-                 frame_chunk: int = 8):
+                 frame_chunk: int = 8, postprocess_on_device: bool = True):
         if model.arena is None:
             raise RuntimeError("call SAM2Model.load(device) before building a predictor")
         object.__setattr__(self, "model", model)
@@ -112,6 +136,8 @@ class SAM2VideoPredictor:
         self.binarize_mask_from_pts_for_mem_enc = binarize_mask_from_pts_for_mem_enc
         self.maskmem_storage_dtype = maskmem_storage_dtype
         self.frame_chunk = max(1, int(frame_chunk))
+        # hole filling by the HIP kernels (stream-ordered, no copy); False: the host scipy path (A/B, tests)
+        self.postprocess_on_device = bool(postprocess_on_device)
         # keep every mask token's low-res logits of the three-mask heads in the frame outputs
         self.keep_multimask_candidates = False
         model.eval()
@@ -383,7 +409,8 @@ class SAM2VideoPredictor:
         if run_mem_encoder:
             mfeat, mpos = self._encode(feat, high, score, O, point_inputs is not None)
         if self.fill_hole_area > 0:
-            low = fill_holes_in_mask_scores(low, self.fill_hole_area)
+            low = fill_holes_in_mask_scores(low, self.fill_hole_area) if self.postprocess_on_device else \
+                _fill_holes_host(low, self.fill_hole_area)
         outs = []
         for i in range(O):
             outs.append({"maskmem_features": None if mfeat is None else mfeat[i:i + 1],
@@ -553,7 +580,7 @@ UPSTREAM_MULTIMASK_OVERRIDES = {
 
 def build_sam2_video_predictor(config_file, ckpt_path=None, device="cuda", mode="eval", hydra_overrides_extra=(),
                                apply_postprocessing=True, vos_optimized=False, compute_dtype="bf16", image_size=None,
-                               multimask: bool = False, **kwargs):
+                               multimask: bool = False, postprocess_on_device: bool = True, **kwargs):
     """upstream sam2.build_sam.build_sam2_video_predictor: the SAM2.1 model of `config_file`
     (named sizes, upstream config names or a YAML path, model/build.py) with `ckpt_path`
     weights (deterministic synthetic weights when absent, as everywhere offline), as a
@@ -561,7 +588,8 @@ def build_sam2_video_predictor(config_file, ckpt_path=None, device="cuda", mode=
     of area <= 8).  `multimask=True` applies UPSTREAM_MULTIMASK_OVERRIDES -- what upstream's released
     configs and builder do: three candidate masks on a single click and on tracked frames (the one of
     highest predicted IoU wins and its token is the object pointer), the stability fallback on box /
-    multi-click prompts.  The default keeps the single-mask heads of the training configuration."""
+    multi-click prompts.  The default keeps the single-mask heads of the training configuration.
+    `postprocess_on_device=False` runs the hole filling on the host (scipy) instead of the HIP kernels."""
     from .model.sam2model import SAM2Model, merge_model_overrides
     if multimask:
         kwargs["model_overrides"] = merge_model_overrides(UPSTREAM_MULTIMASK_OVERRIDES,
@@ -572,4 +600,4 @@ def build_sam2_video_predictor(config_file, ckpt_path=None, device="cuda", mode=
     if mode == "eval":
         model.eval()
     return SAM2VideoPredictor(model, fill_hole_area=8 if apply_postprocessing else 0,
-                              binarize_mask_from_pts_for_mem_enc=True)
+                              binarize_mask_from_pts_for_mem_enc=True, postprocess_on_device=postprocess_on_device)
