@@ -73,6 +73,15 @@ int s2h_trace_marker(int tag, hipStream_t st);
  * fp32 accumulate; dt_c BF16 or F32).  bias_mode 1 = per column, 2 = per row.
  * aux_mode 1 stores the pre-activation into X; 2 multiplies by act'(X) (the
  * activation gradient of the layer that produced X) instead of applying act.
+ * Element types: R and X have the A / B element type dt_ab, NOT the output type dt_c -- a bf16 GEMM
+ * with an fp32 C reads R and reads / writes X as bf16, the fp32 GEMM as fp32; bias and cscale are fp32.
+ * Order per element: v = alpha * acc + bias; X = v (aux_mode 1); v = act(v) or v * act'(X) (aux_mode 2);
+ * v *= cscale[n]; dropout; + R; + beta * C; one rounding to dt_c.
+ * Dropout: counter hash of (seed folded with the bound RNG offset, element index), csrc/common.h; the
+ * drop probability is quantised to 1/65536: an element is dropped with probability
+ * floor(drop_p * 65536) / 65536 (kept values are still scaled by 1 / (1 - drop_p)).  The same holds at
+ * every dropout site of this header (s2h_dropout, s2h_act_dropout_bwd, s2h_linear_add_ln, s2h_ffn_fwd,
+ * attention).
  * Replaces every nn.Linear / 1x1 nn.Conv2d / im2col conv / matmul on the path:
  *   hieradet.py:56-81 (qkv, proj), :140 (dim-change proj), sam2_utils.py:112-139 (MLP),
  *   transformer.py:230-243, 275-311 (q/k/v/out proj), memory_attention.py:58-99 (FFN),
@@ -189,7 +198,8 @@ int s2h_mx8_quant(int rows, int cols, int dt_x, const void* X, int64_t ld_row, i
  * and B [N, K] (ldb, SB, lsb >= N) as s2h_mx8_quant writes them; K is the logical depth (both
  * operands zero-padded to a multiple of 128).  Epilogue as s2h_gemm with bias per column:
  * act (aux_mode 1 stores the pre-activation to X, 2 multiplies by act'(X)), dropout, residual R,
- * beta.  C bf16 (dt_c 1) or fp32 (0). */
+ * beta.  C bf16 (dt_c 1) or fp32 (0); R and X are bf16 whatever dt_c is (row strides ldr / ldx in
+ * elements); the dropout probability is quantised to 1/65536 as in s2h_gemm. */
 int s2h_gemm_mx8(int M, int N, int K, const uint8_t* A, int64_t lda, const int32_t* SA, int64_t lsa,
                  const uint8_t* B, int64_t ldb, const int32_t* SB, int64_t lsb, void* C, int dt_c, int64_t ldc,
                  const float* bias, const void* R, int64_t ldr, void* X, int64_t ldx, int aux_mode, float drop_p,

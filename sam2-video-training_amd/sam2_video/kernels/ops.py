@@ -202,10 +202,21 @@ def deferred_grad_sums(sink):
 
 
 # ----------------------------------------------------------------- GEMM
+def _operand_dtype(what, t, want):
+    """the GEMM epilogues read the residual and the saved pre-activation as the A / B element type
+    (bf16 for the MX-fp8 kernel) whatever the output type, and the column scale as fp32: a tensor of
+    another type would be misread silently, so it is refused here"""
+    if t is not None and t.dtype != want:
+        raise TypeError(f"libsam2hip GEMM: {what} must be {want} (the kernel reads it as that type), got {t.dtype}")
+
+
 def gemm(a, b, c, *, M, N, K, lda_m, lda_k, ldb_k, ldb_n, ldc, batch=1, sA=0, sB=0, sC=0,
          bias=None, bias_mode=1, residual=None, ldr=0, sR=0, aux=None, ldx=0, sX=0, aux_mode=0,
          cscale=None, drop_p=0.0, seed=0, alpha=1.0, beta=0.0, act=0, drop_idx0=0):
-    _dev(a, b, c, bias, residual, aux)
+    _operand_dtype("residual", residual, a.dtype)
+    _operand_dtype("aux", aux, a.dtype)
+    _operand_dtype("cscale", cscale, torch.float32)
+    _dev(a, b, c, bias, residual, aux, cscale)
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.is_contiguous()
     if c.dtype == torch.float32 and K >= 512 and "t" not in _WG_WS:
@@ -521,6 +532,8 @@ def gemm_mx8(a: MX8, b: MX8, c, *, bias=None, residual=None, aux=None, aux_mode=
     assert a.k == b.k and c.dim() == 2 and c.stride(1) == 1
     M, N = a.rows, b.rows
     assert c.shape == (M, N)
+    _operand_dtype("residual", residual, torch.bfloat16)
+    _operand_dtype("aux", aux, torch.bfloat16)
     _dev(a.q, b.q, c, bias, residual, aux)
     call("s2h_gemm_mx8", M, N, a.k, ptr(a.q), a.q.stride(0), ptr(a.s), a.s.stride(0), ptr(b.q), b.q.stride(0),
          ptr(b.s), b.s.stride(0), ptr(c), dt(c), c.stride(0), ptr(bias), ptr(residual),
