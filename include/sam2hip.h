@@ -633,6 +633,34 @@ int s2h_cc_label(int N, int H, int W, const float* scores, int positive, int* la
  * scratch; out must not alias scores; max_area >= 1; sizes as for s2h_cc_label. */
 int s2h_fill_holes(int N, int H, int W, const float* scores, int max_area, float* out, int* work,
                    hipStream_t st);
+/* Category-merged masks of a tracked frame, bit-packed, without materialising the [N, H, W] logits
+ * (reference sam2_video/eval/inference.py:487-514, per object `(out_mask_logits[i] > 0.0).cpu().numpy()` and
+ * `torch.sigmoid(out_mask_logits[i]).mean().item()`, and :870-886, the `key % MOD` OR on the host).
+ * low [N, hi, wi] fp32 low-res logits; every video-resolution value is the one s2h_bilinear_fwd(N, hi, wi, H,
+ * W) computes, bit for bit.  non_overlap: per pixel the object of the highest value keeps it (first index on
+ * a tie, torch.argmax), every other object is clamped to <= -10 (upstream
+ * _apply_non_overlapping_constraints).  cat_off [Ncat + 1] / cat_obj: the object -> category CSR of
+ * s2h_group_max_fwd (an empty category is allowed, a category reads at most N entries).
+ * bits [Ncat, ceil(H W / 64)] uint64: bit j % 64 of word j / 64 of a category is set when an object of the
+ * category is > 0 (0.0 and -0.0 are background) at pixel (y = j % H, x = j / H): COLUMN-major, the order of
+ * COCO RLE; bits past H W are zero.  score [N] = mean over the H W final values of sigmoid(v), fp32, summed in
+ * a fixed order (no float atomics: bit-reproducible).  work: N * ceil(H W / 256) fp32 of scratch.
+ * H, W >= 1, H * W <= 2^24, Ncat * H * W < 2^31 - 256. */
+int s2h_mask_export(int N, int hi, int wi, int H, int W, const float* low, int Ncat, const int* cat_off,
+                    const int* cat_obj, int non_overlap, uint64_t* bits, float* score, float* work,
+                    hipStream_t st);
+/* Run boundaries, area and bounding box of Ncat bit-packed column-major masks (reference inference.py:887-897,
+ * `mask.sum()`, maskUtils.encode(np.asfortranarray(mask)) and eval/utils.py:156-165 mask_to_bbox).  A
+ * transition is a position j in [0, H W) with m[j] != m[j - 1], m[-1] = 0; the RLE counts are the differences
+ * of [0, *transitions, H W].  bits as s2h_mask_export writes them (bits past H W in a last word are ignored).
+ * hdr [Ncat, 8] int32 = n_trans, offset, area, xmin, ymin, xmax, ymax (inclusive corners; W, H, -1, -1 for an
+ * empty mask), total; trans[offset[c] .. offset[c] + n_trans[c]) = the positions of category c, ascending,
+ * the categories back to back.  total = the sum of n_trans = the capacity needed: when it exceeds `capacity`
+ * only the first `capacity` positions are written (nothing past the end) and the caller runs again with a
+ * larger buffer; the header is complete either way.  work: 7 * Ncat * ceil(ceil(H W / 64) / 256) int32 of
+ * scratch.  Integer arithmetic in a fixed order, every device loop bounded; sizes as for s2h_mask_export. */
+int s2h_rle_transitions(int Ncat, int H, int W, const uint64_t* bits, int capacity, int* hdr, int* trans,
+                        int* work, hipStream_t st);
 /* The first upscaling step in one pass (mask_decoder.py:105-106, bf16, Co = 64): pre = the s2h_convt2_store
  * values, y / mean / rstd = LayerNorm2d(pre) over the channels (gamma, beta, eps; the values of
  * s2h_layernorm_fwd), post = gelu(y) (as s2h_act_fwd rounds it); mean / rstd [B * 2H * 2W] fp32. */

@@ -38,20 +38,25 @@ def counts_from_string(s: str) -> List[int]:
 
 
 def counts_to_string(cnts: List[int]) -> str:
-    out = []
-    for i, x in enumerate(cnts):
-        x = int(x)
-        if i > 2:
-            x -= int(cnts[i - 2])
-        more = 1
-        while more:
-            c = x & 0x1F
-            x >>= 5
-            more = (x != -1) if (c & 0x10) else (x != 0)
-            if more:
-                c |= 0x20
-            out.append(chr(c + 48))
-    return "".join(out)
+    # all counts at once, one 5-bit group per pass (an int64 has at most 13): a frame's export encodes tens
+    # of thousands of runs, once per category
+    orig = np.asarray(cnts, dtype=np.int64).reshape(-1)
+    x = orig.copy()
+    if x.size > 3:
+        x[3:] -= orig[1:-2]
+    chars = np.zeros((x.size, 13), dtype=np.uint8)
+    used = np.zeros((x.size, 13), dtype=bool)
+    alive = np.ones(x.size, dtype=bool)
+    for k in range(13):
+        if not alive.any():
+            break
+        c = x & 0x1F
+        x = x >> 5
+        more = np.where((c & 0x10) != 0, x != -1, x != 0) & alive
+        chars[:, k] = (c | (more.astype(np.int64) << 5)) + 48
+        used[:, k] = alive
+        alive = more
+    return chars[used].tobytes().decode("ascii")
 
 
 def _as_rle(rle: Union[Dict, str]) -> Dict:
@@ -91,6 +96,21 @@ def encode(mask: np.ndarray) -> Dict:
     if flat.size and flat[0]:
         runs = [0] + runs
     return {"size": [h, w], "counts": counts_to_string(runs)}
+
+
+def counts_from_transitions(trans, n_pixels: int) -> List[int]:
+    """run lengths from run boundaries: `trans` are the ascending positions j in [0, n_pixels) of the
+    column-major flattened mask with m[j] != m[j - 1] (m[-1] = 0), as s2h_rle_transitions writes them; the
+    counts are the differences of [0, *trans, n_pixels].  A mask whose first pixel is set has trans[0] == 0
+    and so a first count of 0, as pycocotools writes it."""
+    t = np.asarray(trans, dtype=np.int64).reshape(-1)
+    bounds = np.concatenate([[0], t, [int(n_pixels)]])
+    return np.diff(bounds).tolist()
+
+
+def from_transitions(trans, h: int, w: int) -> Dict:
+    """run boundaries of an [h, w] mask -> compressed RLE dict (the dict `encode` gives for that mask)"""
+    return {"size": [int(h), int(w)], "counts": counts_to_string(counts_from_transitions(trans, int(h) * int(w)))}
 
 
 def area(rle) -> int:

@@ -1246,6 +1246,69 @@ def fill_holes(scores, max_area, out=None):
     return out
 
 
+RLE_HDR = 8  # int32 per category of s2h_rle_transitions' header (csrc/rle_scan.h)
+
+
+def rle_words(H, W):
+    """uint64 words of one bit-packed H x W mask"""
+    return (int(H) * int(W) + 63) // 64
+
+
+def mask_export(low, H, W, cat_off, cat_obj, ncat, non_overlap=False, bits=None, scores=None):
+    """category-merged bit masks and per-object scores of one frame (s2h_mask_export).  low [N, hi, wi] fp32
+    contiguous low-res logits; cat_off [ncat + 1] / cat_obj int32: the object -> category CSR.
+    -> (bits [ncat, ceil(H W / 64)] int64 holding the uint64 words of the column-major masks, bit j = pixel
+    (j % H, j // H); scores [N] fp32 = mean sigmoid of the video-resolution logits).  The scratch comes from
+    the torch allocator, so the call can be captured in a HIP graph."""
+    assert low.dim() == 3 and low.dtype == torch.float32 and low.is_contiguous()
+    assert cat_off.dtype == torch.int32 and cat_obj.dtype == torch.int32 and cat_off.numel() == ncat + 1
+    assert cat_off.is_contiguous() and cat_obj.is_contiguous()
+    _dev(low, cat_off, cat_obj)
+    N, hi, wi = low.shape
+    H, W = int(H), int(W)
+    nw = rle_words(H, W)
+    if bits is None:
+        bits = torch.empty(ncat, nw, device=low.device, dtype=torch.int64)
+    if scores is None:
+        scores = torch.empty(N, device=low.device, dtype=torch.float32)
+    assert bits.shape == (ncat, nw) and bits.dtype == torch.int64 and bits.is_contiguous()
+    assert scores.numel() == N and scores.dtype == torch.float32 and scores.is_contiguous()
+    _dev(bits, scores)
+    work = torch.empty(max(1, N * ((H * W + 255) // 256)), device=low.device, dtype=torch.float32)
+    call("s2h_mask_export", N, hi, wi, H, W, ptr(low), ncat, ptr(cat_off), ptr(cat_obj), int(bool(non_overlap)),
+         ptr(bits), ptr(scores), ptr(work), stream())
+    return bits, scores
+
+
+def rle_transitions(bits, H, W, capacity=None, hdr=None, trans=None):
+    """run boundaries, area and bounding box of bit-packed column-major masks (s2h_rle_transitions).
+    bits [ncat, ceil(H W / 64)] int64.  -> (hdr [ncat, 8] int32 = n_trans, offset, area, xmin, ymin, xmax,
+    ymax, total per category; trans [capacity] int32: category c's positions at offset[c] ..).  When
+    total > capacity only the first `capacity` positions were written: call again with capacity >= total.
+    capacity None = the worst case ncat * H * W."""
+    assert bits.dim() == 2 and bits.dtype == torch.int64 and bits.is_contiguous()
+    _dev(bits)
+    ncat = bits.shape[0]
+    H, W = int(H), int(W)
+    nw = rle_words(H, W)
+    assert bits.shape[1] == nw
+    if trans is not None:
+        capacity = trans.numel()
+    elif capacity is None:
+        capacity = ncat * H * W
+    capacity = int(capacity)
+    if hdr is None:
+        hdr = torch.empty(ncat, RLE_HDR, device=bits.device, dtype=torch.int32)
+    if trans is None:
+        trans = torch.empty(capacity, device=bits.device, dtype=torch.int32)
+    assert hdr.numel() == ncat * RLE_HDR and hdr.dtype == torch.int32 and hdr.is_contiguous()
+    assert trans.dtype == torch.int32 and trans.is_contiguous()
+    _dev(hdr, trans)
+    work = torch.empty(max(1, 7 * ncat * ((nw + 255) // 256)), device=bits.device, dtype=torch.int32)
+    call("s2h_rle_transitions", ncat, H, W, ptr(bits), capacity, ptr(hdr), ptr(trans), ptr(work), stream())
+    return hdr, trans
+
+
 def convt2_gather(dout, B, H, W, Co, dY=None):
     if dY is None:
         dY = torch.empty(B * H * W, 4 * Co, device=dout.device, dtype=dout.dtype)

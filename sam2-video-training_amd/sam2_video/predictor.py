@@ -20,7 +20,10 @@ published SAM2.1 algorithm (sam2/sam2_video_predictor.py):
   * memory features are stored in bf16 (as upstream stores them), low-res mask logits in fp32;
   * optional hole filling of the low-res logits (`fill_hole_area`, 8 in build_sam2_video_predictor):
     connected components and the fill are HIP kernels (csrc/cc.hip), stream-ordered between the SAM
-    heads and the bilinear upsampling; `postprocess_on_device=False` keeps the host scipy path for A/B.
+    heads and the bilinear upsampling; `postprocess_on_device=False` keeps the host scipy path for A/B;
+  * `propagate_in_video_export` is the same tracking loop feeding the evaluation's predict.json
+    (eval/inference.py): per frame a MergedFrame -- category-merged COCO RLE run boundaries, area, box and
+    per-object scores from csrc/rle.hip -- instead of video-resolution logits.
 
 MI355X-first choices (not observable in the outputs): objects whose conditioning / tracked frame
 sets agree are run as ONE batch through the kernels instead of one object at a time (each object
@@ -118,6 +121,91 @@ def _fill_holes_host(mask: torch.Tensor, max_area: int) -> torch.Tensor:
     return torch.from_numpy(m).to(mask.device)
 
 
+class StagingPool:
+    """Pinned host blocks with an event each, for the export's device -> host copies.  A block is taken per
+    frame and given back by MergedFrame.result(), so a clip reuses the one or two blocks of its first frames:
+    tracking allocates no pinned memory per frame and creates no event per frame.  An inference state owns one
+    pool (init_state) and keeps it as long as it lives."""
+
+    def __init__(self):
+        self._free = {}  # number of int32 -> [(pinned tensor, event)]
+
+    def take(self, n):
+        free = self._free.get(n)
+        if free:
+            return free.pop()
+        return torch.empty(n, dtype=torch.int32, pin_memory=True), torch.cuda.Event()
+
+    def give(self, n, slot):
+        self._free.setdefault(n, []).append(slot)
+
+
+class MergedFrame:
+    """One tracked frame's export, in flight: the category-merged masks as COCO RLE run boundaries, their
+    area and bounding box, and the per-object scores (ops.mask_export + ops.rle_transitions on the current
+    stream), one device buffer copied to a pinned block of `pool` behind them, and an event after the copy.
+    Building it waits for nothing; result() waits for the event, decodes on the host and gives the block back.
+
+    The buffer holds `capacity` run boundaries (default: 16 runs per image column and category, at least
+    4096); a frame that needs more is found in result() from the header and extracted again from the bits
+    kept on the device, with a blocking copy -- rare, and still exact.  The whole buffer is copied whatever
+    the frame uses of it (656 KB at 1024 x 1280 and 4 categories, of which ~96 KB are typically positions):
+    copying only the used part would need the header on the host first, a second round trip per frame."""
+
+    def __init__(self, low, H, W, obj_ids, cat_ids, cat_off, cat_obj, non_overlap=False, capacity=None, pool=None):
+        ncat, N = len(cat_ids), low.shape[0]
+        self.low_res_logits = low  # [N, h, w] fp32 (what a probability dump upsamples)
+        self.height, self.width, self.obj_ids, self.cat_ids = int(H), int(W), list(obj_ids), list(cat_ids)
+        self.capacity = int(capacity) if capacity is not None else max(4096, 32 * self.width * ncat)
+        n_hdr = ncat * ops.RLE_HDR
+        buf = torch.empty(n_hdr + N + self.capacity, device=low.device, dtype=torch.int32)
+        self.bits, _ = ops.mask_export(low, H, W, cat_off, cat_obj, ncat, non_overlap,
+                                       scores=buf[n_hdr:n_hdr + N].view(torch.float32))
+        ops.rle_transitions(self.bits, H, W, hdr=buf[:n_hdr], trans=buf[n_hdr + N:])
+        self._pool = pool if pool is not None else StagingPool()
+        self.staging, self.event = self._pool.take(buf.numel())
+        self.staging.copy_(buf, non_blocking=True)
+        self.event.record()
+        self.bytes_copied = buf.numel() * 4
+        self._result = None
+
+    def result(self):
+        """{"categories": {cat_id: {"segmentation": {"size": [H, W], "counts": str}, "bbox": [xmin, ymin,
+        xmax, ymax] (floats, the reference's mask_to_bbox corners), "area": int}} for the non-empty
+        categories in first-seen order of the objects, "scores": {obj_id: float}}"""
+        if self._result is not None:
+            return self._result
+        from .data import rle
+        self.event.synchronize()
+        ncat, N = len(self.cat_ids), len(self.obj_ids)
+        a = self.staging.numpy()
+        n_hdr = ncat * ops.RLE_HDR
+        hdr = a[:n_hdr].reshape(ncat, ops.RLE_HDR)
+        scores = a[n_hdr:n_hdr + N].view(np.float32)
+        trans = a[n_hdr + N:]
+        if ncat and int(hdr[0, 7]) > self.capacity:  # overflow: the header says how much room is needed
+            # (the bits were written on the stream of __init__, which the event follows: order this stream,
+            # whichever it is by now, behind it)
+            torch.cuda.current_stream().wait_event(self.event)
+            _, t = ops.rle_transitions(self.bits, self.height, self.width, capacity=int(hdr[0, 7]))
+            trans = t.cpu().numpy()
+            self.bytes_copied += trans.size * 4
+        cats = OrderedDict()
+        for c, cat in enumerate(self.cat_ids):
+            n, off, area, xmin, ymin, xmax, ymax = (int(v) for v in hdr[c, :7])
+            if area == 0:
+                continue
+            cats[cat] = {"segmentation": rle.from_transitions(trans[off:off + n], self.height, self.width),
+                         "bbox": [float(xmin), float(ymin), float(xmax), float(ymax)], "area": area}
+        self._result = {"categories": cats,
+                        "scores": OrderedDict((i, float(v)) for i, v in zip(self.obj_ids, scores))}
+        self.runs_total = int(hdr[0, 7]) if ncat else 0
+        # everything is decoded into Python objects: the block goes back to the pool for the next frame
+        self._pool.give(a.size, (self.staging, self.event))
+        self.staging = self.event = self.bits = self._pool = None
+        return self._result
+
+
 class SAM2VideoPredictor:
     """Wraps a loaded SAM2Model (every nn.Module attribute -- sam_mask_decoder, image_size,
     state_dict, ... -- is reachable on the predictor, as on upstream's SAM2Base subclass)."""
@@ -178,6 +266,7 @@ class SAM2VideoPredictor:
             "cached_features": {}, "constants": {}, "obj_id_to_idx": OrderedDict(),
             "obj_idx_to_id": OrderedDict(), "obj_ids": [], "output_dict_per_obj": {},
             "temp_output_dict_per_obj": {}, "frames_tracked_per_obj": {}, "tracking_has_started": False,
+            "export_staging": StagingPool(),  # propagate_in_video_export's pinned blocks, reused frame after frame
         }
         self._get_image_feature(state, 0)  # warm up the backbone, as upstream does
         return state
@@ -477,9 +566,52 @@ class SAM2VideoPredictor:
     def propagate_in_video(self, inference_state, start_frame_idx=None, max_frame_num_to_track=None,
                            reverse=False):
         s = inference_state
+        for t, masks in self._propagate(s, start_frame_idx, max_frame_num_to_track, reverse):
+            yield t, s["obj_ids"], self._video_res(s, masks)
+
+    @torch.no_grad()
+    def propagate_in_video_export(self, inference_state, obj_to_cat, start_frame_idx=None,
+                                  max_frame_num_to_track=None, reverse=False):
+        """propagate_in_video for the evaluation's export (reference eval/inference.py:487-514 + :870-901):
+        the same tracking, but instead of [N, 1, H, W] logits every frame yields
+        (frame_idx, obj_ids, MergedFrame): the objects' masks OR-ed per category (`obj_to_cat`: a dict or a
+        callable obj_id -> category id), as COCO RLE run boundaries with area, bounding box and the
+        per-object scores, computed by csrc/rle.hip from the low-res logits on the current stream
+        (`non_overlap_masks` honoured).  The video-resolution logits are never stored and nothing here waits
+        for the device: MergedFrame.result() does, when the caller asks."""
+        s = inference_state
+        for t, masks in self._propagate(s, start_frame_idx, max_frame_num_to_track, reverse):
+            yield t, s["obj_ids"], self._export_frame(s, masks, obj_to_cat)
+
+    def _export_csr(self, s, obj_to_cat):
+        """(category ids in first-seen order of the objects, cat_off, cat_obj on the device)"""
+        ids = list(s["obj_ids"])
+        cats = [obj_to_cat(i) if callable(obj_to_cat) else obj_to_cat[i] for i in ids]
+        key = ("export_csr", tuple(ids), tuple(cats))
+        c = s["constants"].get(key)
+        if c is None:
+            order = list(OrderedDict.fromkeys(cats))
+            members = [[k for k, cat in enumerate(cats) if cat == o] for o in order]
+            off = np.cumsum([0] + [len(m) for m in members]).astype(np.int32)
+            obj = np.asarray([k for m in members for k in m] + [0], dtype=np.int32)  # (never empty)
+            c = s["constants"][key] = (order, torch.from_numpy(off).to(s["device"]),
+                                       torch.from_numpy(obj).to(s["device"]))
+        return c
+
+    def _export_frame(self, s, masks, obj_to_cat):
+        """low-res logits [N, 1, h, w] of a frame -> MergedFrame (kernels and the copy enqueued, not waited for)"""
+        cat_ids, cat_off, cat_obj = self._export_csr(s, obj_to_cat)
+        N, _, h, w = masks.shape
+        H, W = s["video_height"], s["video_width"]
+        low = masks.reshape(N, h, w).contiguous()
+        return MergedFrame(low, H, W, list(s["obj_ids"]), cat_ids, cat_off, cat_obj,
+                           self.non_overlap_masks and N > 1, pool=s["export_staging"])
+
+    def _propagate(self, inference_state, start_frame_idx, max_frame_num_to_track, reverse):
+        """the tracking loop both generators share -> (frame_idx, low-res logits [N, 1, 4h, 4w])"""
+        s = inference_state
         self.propagate_in_video_preflight(s)
-        obj_ids = s["obj_ids"]
-        n = len(obj_ids)
+        n = len(s["obj_ids"])
         T = s["num_frames"]
         if start_frame_idx is None:
             start_frame_idx = min(t for d in s["output_dict_per_obj"].values() for t in d["cond_frame_outputs"])
@@ -511,8 +643,7 @@ class SAM2VideoPredictor:
                     per_obj[i] = out["pred_masks"]
             for i in range(n):
                 s["frames_tracked_per_obj"][i][t] = {"reverse": reverse}
-            masks = torch.cat(per_obj, dim=0) if n > 1 else per_obj[0]
-            yield t, obj_ids, self._video_res(s, masks)
+            yield t, (torch.cat(per_obj, dim=0) if n > 1 else per_obj[0])
 
     @staticmethod
     def _groups(s, obj_idxs) -> List[List[int]]:
