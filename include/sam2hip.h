@@ -649,6 +649,29 @@ int s2h_fill_holes(int N, int H, int W, const float* scores, int max_area, float
 int s2h_mask_export(int N, int hi, int wi, int H, int W, const float* low, int Ncat, const int* cat_off,
                     const int* cat_obj, int non_overlap, uint64_t* bits, float* score, float* work,
                     hipStream_t st);
+/* s2h_mask_export at a tuned threshold: foreground is final value >= cut (NaN is background, -0.0 >= 0.0
+ * holds), cut = the logit cut of a float16 probability threshold (reference export_predict_from_probs.py:66,
+ * `probs[indices] >= threshold` on float16 sigmoids).  Everything else, score included, as s2h_mask_export.
+ * vmax [N] = the maximum over the H W final values of each object, fmaxf from -inf (NaN skipped): the
+ * category's score `probs.max()` of the reference is the float16 sigmoid of the maximum over its objects.
+ * work: 2 * N * ceil(H W / 256) fp32 of scratch. */
+int s2h_mask_export_cut(int N, int hi, int wi, int H, int W, const float* low, int Ncat, const int* cat_off,
+                        const int* cat_obj, int non_overlap, float cut, uint64_t* bits, float* score,
+                        float* vmax, float* work, hipStream_t st);
+/* The threshold sweep of a tracked frame (reference tune_threshold.py:92-110, `np.any(probs[idx] >= thr)` per
+ * category and threshold against the ground truth) for K thresholds in one pass, without the [N, H, W] values.
+ * low, cat_off, cat_obj, non_overlap and the video-resolution values as for s2h_mask_export.  cuts [K] fp32 on
+ * the device, non-decreasing (equal neighbours allowed: their bin stays empty), 1 <= K <= 64.  gt_bits [Ncat,
+ * ceil(H W / 64)] uint64: the ground truth per category in the layout s2h_mask_export writes (bits past H W in
+ * a last word are ignored); NULL = all background.  Per pixel and category m = the maximum over the category's
+ * objects of the final value (NaN skipped, -inf for an empty category) and b = #{k : m >= cuts[k]}.
+ * hist [Ncat, 2, K + 1] int32, overwritten: hist[c][g][b] = the pixels with ground-truth bit g in bin b, so
+ * every row pair sums to H W and the pixels counting at cut k are the bins above k.  Integer counting (ballot
+ * and popcount per wave, integer atomics): a pure function of the inputs, every device loop bounded; sizes as
+ * for s2h_mask_export. */
+int s2h_mask_sweep(int N, int hi, int wi, int H, int W, const float* low, int Ncat, const int* cat_off,
+                   const int* cat_obj, int non_overlap, int K, const float* cuts, const uint64_t* gt_bits,
+                   int* hist, hipStream_t st);
 /* Run boundaries, area and bounding box of Ncat bit-packed column-major masks (reference inference.py:887-897,
  * `mask.sum()`, maskUtils.encode(np.asfortranarray(mask)) and eval/utils.py:156-165 mask_to_bbox).  A
  * transition is a position j in [0, H W) with m[j] != m[j - 1], m[-1] = 0; the RLE counts are the differences

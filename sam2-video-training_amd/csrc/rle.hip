@@ -12,6 +12,12 @@
 //   one over the objects for the sigmoid sums, one over the categories' object lists for the bits.
 //   The sigmoid sums are reduced in a fixed order: butterfly within the wave, the four waves in order, one
 //   partial per workgroup and object, then det_colsum (reduce_det.h).  No atomics.
+// s2h_mask_export_cut: the same kernel body (a template flag) with foreground `value >= cut` for a tuned
+//   threshold (eval/tune_threshold.py logit_cuts) and the per-object maximum value, reduced like the sums
+//   (fmaxf per wave, workgroup, then over the workgroups).
+// s2h_mask_sweep: the threshold sweep.  The same pixel mapping and values; per category the maximum over
+//   its objects is binned against K cuts and counted per bin and ground-truth bit (sweep_hist.h): the wave's
+//   ground-truth word is one load, a bin's pixels one ballot and two popcounts.  Integer adds only.
 // s2h_rle_transitions: count / scan / emit over the words (rle_scan.h), 256 words per workgroup:
 //   1. per word the popcount of its transition mask and its area / bounding box, reduced per workgroup;
 //   2. one workgroup scans the workgroup counts (exclusive, over words then categories) and folds the
@@ -22,12 +28,18 @@
 #include "common.h"
 #include "reduce_det.h"
 #include "rle_scan.h"
+#include "sweep_hist.h"
 
 namespace {
 
 __device__ __forceinline__ float wave_sum_f(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max_f(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
 __device__ __forceinline__ int wave_sum_i(int v) {
@@ -48,10 +60,15 @@ __device__ __forceinline__ int wave_max_i(int v) {
 
 // part[blockIdx.x][i] = (sum over the workgroup's pixels of sigmoid(final value of object i)) / (H W);
 // bits[c][word] = OR over the objects of category c of (final value > 0)
+// CUT (s2h_mask_export_cut): foreground is final value >= cut instead, and pmax[blockIdx.x][i] = the maximum
+// over the workgroup's pixels of the final value of object i (fmaxf from -inf: NaN is skipped)
+template <bool CUT>
 __global__ __launch_bounds__(256) void mask_export_kernel(int N, int hi, int wi, int H, int W, const float* low,
                                                           int Ncat, const int* cat_off, const int* cat_obj,
-                                                          int non_overlap, uint64_t* bits, int nw, float* part) {
+                                                          int non_overlap, uint64_t* bits, int nw, float* part,
+                                                          float cut, float* pmax) {
   __shared__ float red[2][4];
+  __shared__ float redm[2][4];
   const int HW = H * W;
   const int j = blockIdx.x * 256 + threadIdx.x;  // (the host checked H W <= 2^24)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -86,9 +103,17 @@ __global__ __launch_bounds__(256) void mask_export_kernel(int N, int hi, int wi,
     if (arg >= 0 && i != arg) v = fminf(v, -10.f);
     const float s = wave_sum_f(in ? 1.f / (1.f + expf(-v)) : 0.f);
     if (lane == 0) red[i & 1][wave] = s;
+    if (CUT) {
+      const float mx = wave_max_f(in ? v : -INFINITY);
+      if (lane == 0) redm[i & 1][wave] = mx;
+    }
     __syncthreads();  // (one barrier per object: iteration i + 2 rewrites red[i & 1] after the next barrier)
-    if (threadIdx.x == 0)
+    if (threadIdx.x == 0) {
       part[(int64_t)blockIdx.x * N + i] = ((red[i & 1][0] + red[i & 1][1]) + (red[i & 1][2] + red[i & 1][3])) * inv_n;
+      if (CUT)
+        pmax[(int64_t)blockIdx.x * N + i] =
+            fmaxf(fmaxf(redm[i & 1][0], redm[i & 1][1]), fmaxf(redm[i & 1][2], redm[i & 1][3]));
+    }
   }
 
   const int word = j >> 6;  // the same for the 64 lanes of a wave
@@ -101,10 +126,87 @@ __global__ __launch_bounds__(256) void mask_export_kernel(int N, int hi, int wi,
       if ((unsigned)o >= (unsigned)N) continue;
       float v = bil_tap(low + o * plane, wi, y0, y1, x0, x1, ly, lx);
       if (arg >= 0 && o != arg) v = fminf(v, -10.f);
-      fg = fg || v > 0.f;  // 0.0, -0.0 and NaN are background
+      fg = fg || (CUT ? v >= cut : v > 0.f);  // 0.0, -0.0 and NaN are background (CUT: NaN is, -0.0 >= 0.0)
     }
     const uint64_t m = __ballot(in && fg);  // bits past H W stay zero
     if (lane == 0 && word < nw) bits[(int64_t)c * nw + word] = m;
+  }
+}
+
+// out[i] = max over the nr rows of pmax[r][i] (fmaxf: any order gives the same value); one workgroup per i
+__global__ __launch_bounds__(256) void colmax_kernel(int nr, int N, const float* pmax, float* out) {
+  __shared__ float red[4];
+  const int i = blockIdx.x;
+  float m = -INFINITY;
+  for (int r = threadIdx.x; r < nr; r += 256) m = fmaxf(m, pmax[(int64_t)r * N + i]);
+  m = wave_max_f(m);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) out[i] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// hist[c][g][b] += the workgroup's pixels of category c with ground-truth bit g whose merged value (the
+// maximum over the category's objects of the final value, NaN skipped, -inf for no object) lies in bin b
+// (sweep_hist.h).  The pixel mapping, the taps and the non-overlap clamp are mask_export_kernel's; a
+// workgroup is SWEEP_BLOCK pixels = 16 words.  hist is zero on entry.
+__global__ __launch_bounds__(SWEEP_BLOCK) void mask_sweep_kernel(int N, int hi, int wi, int H, int W, const float* low,
+                                                                 int Ncat, const int* cat_off, const int* cat_obj,
+                                                                 int non_overlap, int K, const float* cuts,
+                                                                 const uint64_t* gt_bits, int nw, int* hist) {
+  __shared__ int blk[2 * (SWEEP_MAX_K + 1)];
+  __shared__ float scut[SWEEP_MAX_K];
+  if ((int)threadIdx.x < K) scut[threadIdx.x] = cuts[threadIdx.x];
+  if ((int)threadIdx.x < 2 * (K + 1)) blk[threadIdx.x] = 0;
+  __syncthreads();
+  const int HW = H * W;
+  const int j = blockIdx.x * SWEEP_BLOCK + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool in = j < HW;
+  const int jj = in ? j : HW - 1;
+  const int x = jj / H, y = jj - x * H;
+  const float sh = (float)hi / H, sw = (float)wi / W;
+  int y0, y1, x0, x1;
+  float ly, lx;
+  bil_src(y, sh, hi, y0, y1, ly);
+  bil_src(x, sw, wi, x0, x1, lx);
+  const int64_t plane = (int64_t)hi * wi;
+
+  int arg = -1;  // as mask_export_kernel
+  if (non_overlap && N > 0) {
+    float best = bil_tap(low, wi, y0, y1, x0, x1, ly, lx);
+    arg = 0;
+    for (int i = 1; i < N; ++i) {
+      const float v = bil_tap(low + i * plane, wi, y0, y1, x0, x1, ly, lx);
+      if (v > best) {
+        best = v;
+        arg = i;
+      }
+    }
+  }
+
+  const int word = j >> 6;  // the same for the 64 lanes of a wave
+  const uint64_t valid = __ballot(in);
+  for (int c = 0; c < Ncat; ++c) {
+    const int k0 = cat_off[c];
+    const int k1 = min(cat_off[c + 1], k0 + N);
+    float m = -INFINITY;
+    for (int k = k0; k < k1; ++k) {
+      const int o = cat_obj[k];
+      if ((unsigned)o >= (unsigned)N) continue;
+      float v = bil_tap(low + o * plane, wi, y0, y1, x0, x1, ly, lx);
+      if (arg >= 0 && o != arg) v = fminf(v, -10.f);
+      m = fmaxf(m, v);  // (fmaxf returns the other operand for a NaN)
+    }
+    const int b = sweep_bin(m, scut, K);
+    // one load per wave; a wave entirely past H W has valid == 0 and reads nothing
+    const uint64_t gt = (gt_bits && valid) ? gt_bits[(int64_t)c * nw + word] : 0ull;
+    for (int q = 0; q <= K; ++q) {
+      const uint64_t sel = __ballot(in && b == q);
+      if (sel && lane == 0) sweep_block_add(blk, K, q, sweep_word_counts(sel, gt));
+    }
+    __syncthreads();
+    sweep_block_flush(hist + (int64_t)c * 2 * (K + 1), blk, K, threadIdx.x, SWEEP_BLOCK);
+    __syncthreads();
   }
 }
 
@@ -240,9 +342,43 @@ extern "C" int s2h_mask_export(int N, int hi, int wi, int H, int W, const float*
   if ((N > 0 && (!low || !score || !work)) || (Ncat > 0 && (!bits || !cat_off || !cat_obj)))
     return (int)hipErrorInvalidValue;
   const int nb = (H * W + 255) / 256;
-  hipLaunchKernelGGL(mask_export_kernel, dim3((unsigned)nb), dim3(256), 0, st, N, hi, wi, H, W, low, Ncat, cat_off,
-                     cat_obj, non_overlap, bits, nw, work);
+  hipLaunchKernelGGL(mask_export_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, N, hi, wi, H, W, low, Ncat,
+                     cat_off, cat_obj, non_overlap, bits, nw, work, 0.f, (float*)nullptr);
   if (N > 0) det_colsum(1, nb, N, work, score, 0, st);
+  S2H_LAUNCH_CHECK();
+}
+
+extern "C" int s2h_mask_export_cut(int N, int hi, int wi, int H, int W, const float* low, int Ncat, const int* cat_off,
+                                   const int* cat_obj, int non_overlap, float cut, uint64_t* bits, float* score,
+                                   float* vmax, float* work, hipStream_t st) {
+  const int nw = rle_words(Ncat, H, W);
+  if (nw < 0 || N < 0 || hi < 1 || wi < 1 || (int64_t)N * hi * wi > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  if (N == 0 && Ncat == 0) return 0;
+  if ((N > 0 && (!low || !score || !vmax || !work)) || (Ncat > 0 && (!bits || !cat_off || !cat_obj)))
+    return (int)hipErrorInvalidValue;
+  const int nb = (H * W + 255) / 256;
+  float* pmax = work + (int64_t)nb * N;
+  hipLaunchKernelGGL(mask_export_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, N, hi, wi, H, W, low, Ncat,
+                     cat_off, cat_obj, non_overlap, bits, nw, work, cut, pmax);
+  if (N > 0) {
+    det_colsum(1, nb, N, work, score, 0, st);
+    hipLaunchKernelGGL(colmax_kernel, dim3((unsigned)N), dim3(256), 0, st, nb, N, (const float*)pmax, vmax);
+  }
+  S2H_LAUNCH_CHECK();
+}
+
+extern "C" int s2h_mask_sweep(int N, int hi, int wi, int H, int W, const float* low, int Ncat, const int* cat_off,
+                              const int* cat_obj, int non_overlap, int K, const float* cuts, const uint64_t* gt_bits,
+                              int* hist, hipStream_t st) {
+  const int nw = rle_words(Ncat, H, W);
+  if (nw < 0 || N < 0 || hi < 1 || wi < 1 || (int64_t)N * hi * wi > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  if (K < 1 || K > SWEEP_MAX_K || !cuts) return (int)hipErrorInvalidValue;
+  if (Ncat == 0) return 0;
+  if (!hist || !cat_off || !cat_obj || (N > 0 && !low)) return (int)hipErrorInvalidValue;
+  s2h_zero_f32((float*)hist, 1, (int64_t)Ncat * 2 * (K + 1), (int64_t)Ncat * 2 * (K + 1), st);  // (int 0 = 0.0f bits)
+  const int nb = (H * W + SWEEP_BLOCK - 1) / SWEEP_BLOCK;
+  hipLaunchKernelGGL(mask_sweep_kernel, dim3((unsigned)nb), dim3(SWEEP_BLOCK), 0, st, N, hi, wi, H, W, low, Ncat, cat_off,
+                     cat_obj, non_overlap, K, cuts, gt_bits, nw, hist);
   S2H_LAUNCH_CHECK();
 }
 

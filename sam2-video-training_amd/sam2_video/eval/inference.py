@@ -16,6 +16,13 @@ low-res logits, and only those, six integers per category and one float per obje
 behind the tracking.  `export_on_device=False` is the reference's loop, kept as the A/B path and the tests'
 oracle; save_as_coco_format writes the same file from either.
 
+Threshold tuning runs on the same path: `sweep=` (a tune_threshold.SweepAccumulator) has csrc/rle.hip count,
+per frame and category, the histogram of the merged logits over all candidate thresholds' logit cuts against the
+ground truth -- a few hundred bytes in the frame's one copy instead of the reference's float16 probability dump
+that tune_threshold.grid_search reloads per threshold -- and `threshold=` + save_thresholded_predict write
+export_predict_from_probs.py's `predict_t0.xx.json` at the tuned threshold.  `probs_out_dir` and the two host
+modules stay as the A/B path.
+
 Out of scope: generating the prompts from ground truth (get_each_obj / generate_prompts_by_*: utils.py
 mask_to_masks is cv2.morphologyEx + cv2.connectedComponentsWithStats, and cv2 is not a dependency -- a scipy
 restatement could not be pinned against it) and the top-level `inference()` that drives it from a COCO file.
@@ -79,7 +86,8 @@ def add_prompt(prompt_objs: List[PromptObj], predictor, inference_state, prompt_
 
 
 def predict_on_video(predictor, inference_state, start_idx, frames=None, probs_out_dir: Optional[str] = None, *,
-                     mod: Optional[int] = None, export_on_device: bool = True) -> Dict:
+                     mod: Optional[int] = None, export_on_device: bool = True, threshold: Optional[float] = None,
+                     sweep=None) -> Dict:
     """reverse pass, then forward pass (whose frames overwrite the reverse pass's: the prompt frame carries
     the forward result) -> {order_in_video: frame result}.
 
@@ -93,7 +101,18 @@ def predict_on_video(predictor, inference_state, start_idx, frames=None, probs_o
     float16 sigmoid of the video-resolution logits and the metadata of inference.py:476-485; a tuning aid
     that materialises the logits for that frame in either mode.  One departure from the reference's bytes: a
     positive logit whose sigmoid rounds to exactly 0.5 in float16 (0 < v <= 2^-10) is stored as 0.5 + 2^-11,
-    one float16 step up, so that `probs > 0.5` is `logits > 0`, the mask of predict.json, on every pixel."""
+    one float16 step up, so that `probs > 0.5` is `logits > 0`, the mask of predict.json, on every pixel.
+
+    threshold (export_on_device only): the masks are binarised at that probability as the reference thresholds
+    its float16 dump (export_predict_from_probs.py) and every frame result carries "max_logit" for
+    save_thresholded_predict.  sweep (a tune_threshold.SweepAccumulator; export_on_device, `frames`): every
+    tracked frame's histogram over the accumulator's cuts against its ground truth is counted on the device
+    and added to it -- threshold tuning without a dump.  A frame both passes visit contributes once, from the
+    first visit, as the dump's "skip if the file exists" keeps the reverse pass's probabilities."""
+    if (threshold is not None or sweep is not None) and not export_on_device:
+        raise ValueError("threshold= and sweep= run on the device export (export_on_device=True)")
+    if sweep is not None and frames is None:
+        raise ValueError("sweep= needs `frames` (the image id and size of every frame)")
     video_segments = {}
     frame_meta = None
     if frames is not None:
@@ -132,19 +151,38 @@ def predict_on_video(predictor, inference_state, start_idx, frames=None, probs_o
 
     if mod is None:
         raise ValueError("predict_on_video(export_on_device=True) needs `mod` (category = obj_id % mod)")
+    extra = {}
+    if threshold is not None:
+        extra["threshold"] = threshold
+    if sweep is not None:
+        # the ground truth of the whole clip, packed per category in the export's category order (first-seen
+        # order of the objects), uploaded once
+        if sweep.mod != mod:
+            raise ValueError(f"the accumulator merges with mod {sweep.mod}, the export with {mod}")
+        cat_ids = list(dict.fromkeys(i % mod for i in inference_state["obj_ids"]))
+        gt = np.stack([sweep.gt_bits(frame_meta[t + start_idx][0], cat_ids, *frame_meta[t + start_idx][2:])
+                       for t in range(inference_state["num_frames"])])
+        gt = torch.from_numpy(gt).to(inference_state["device"])
+        extra["sweep_cuts"], extra["gt_bits"] = sweep.cuts, lambda t: gt[t]
+
+    def _collect(order_key, merged):
+        video_segments[order_key] = res = merged.result()
+        if sweep is not None and frame_meta[order_key][0] not in sweep:
+            sweep.add_frame(frame_meta[order_key][0], merged.obj_ids, res["cat_ids"], res["sweep"])
+
     in_flight = None  # (order key, MergedFrame) of the frame enqueued last
     for reverse in (True, False):
         for out_frame_idx, out_obj_ids, merged in predictor.propagate_in_video_export(
-                inference_state, lambda obj_id: obj_id % mod, reverse=reverse):
+                inference_state, lambda obj_id: obj_id % mod, reverse=reverse, **extra):
             order_key = out_frame_idx + start_idx
             if probs_out_dir is not None and frame_meta is not None:
                 _maybe_write_probs(order_key, out_obj_ids,
                                    predictor._video_res(inference_state, merged.low_res_logits[:, None]))
             if in_flight is not None:
-                video_segments[in_flight[0]] = in_flight[1].result()
+                _collect(*in_flight)
             in_flight = (order_key, merged)
     if in_flight is not None:
-        video_segments[in_flight[0]] = in_flight[1].result()
+        _collect(*in_flight)
     return video_segments
 
 
@@ -156,7 +194,8 @@ def _read_frames(paths) -> np.ndarray:
 
 def process_video_clip(predictor, frames, clip_prompts: List[PromptInfo], clip_range: ClipRange,
                        probs_out_dir: Optional[str] = None, *, video=None, mod: Optional[int] = None,
-                       export_on_device: bool = True, finetuned_state_dict=None) -> Dict:
+                       export_on_device: bool = True, finetuned_state_dict=None, threshold: Optional[float] = None,
+                       sweep=None) -> Dict:
     """inference.py:532-577 on a predictor the caller built: init_state on the clip's frames, the clip's
     prompts, predict_on_video.  `frames`: the video's frame dicts (id, video_id, order_in_video, height,
     width, path), indexed by order_in_video as in the reference.  `video`: the clip's images as a list of
@@ -173,7 +212,7 @@ def process_video_clip(predictor, frames, clip_prompts: List[PromptInfo], clip_r
         add_prompt(prompt_info.prompt_objs, predictor, inference_state, prompt_info.frame_idx - start_idx,
                    prompt_info.prompt_type)
     return predict_on_video(predictor, inference_state, start_idx, frames=frames, probs_out_dir=probs_out_dir,
-                            mod=mod, export_on_device=export_on_device)
+                            mod=mod, export_on_device=export_on_device, threshold=threshold, sweep=sweep)
 
 
 def _frame_annotations(image_id, segment, mod) -> List[Dict]:
@@ -225,3 +264,30 @@ def save_as_coco_format(all_video_segments, frames_by_video, mod, eval_dir, prom
     with open(prompt_path, "wb") as f:
         pickle.dump(list(prompt_info or []), f)
     return predict_path, prompt_path
+
+
+def save_thresholded_predict(all_video_segments, frames_by_video, threshold, output_predict: Optional[str] = None,
+                             exclude_background: bool = False) -> str:
+    """what export_predict_from_probs.export_predict writes from a dump, from predict_on_video(threshold=...)'s
+    device results: per frame and non-empty category image_id, category_id, segmentation, bbox, iscrowd 0 and
+    score = the category's maximum float16 probability, float16(sigmoid(max over its objects of max_logit)).
+    indent=2; default name `predict_t{threshold:.2f}.json` (in the working directory).  -> the path"""
+    annotations: List[Dict] = []
+    for video_id, video_segments in all_video_segments.items():
+        for frame in sort_dicts_by_field(frames_by_video[video_id], "order_in_video"):
+            segment = video_segments[frame["order_in_video"]]
+            if "max_logit" not in segment:
+                raise ValueError("save_thresholded_predict needs the results of predict_on_video(threshold=...)")
+            for cat, info in segment["categories"].items():
+                if exclude_background and cat == 0:
+                    continue
+                m = max(float(v) for i, v in segment["max_logit"].items() if segment["obj_cats"][i] == cat)
+                score = float(np.float16(1.0 / (1.0 + np.exp(-np.float64(m)))))
+                annotations.append({"image_id": int(frame["id"]), "category_id": int(cat),
+                                    "segmentation": dict(info["segmentation"]), "bbox": list(info["bbox"]),
+                                    "iscrowd": 0, "score": score})
+    if output_predict is None:
+        output_predict = f"predict_t{threshold:.2f}.json"
+    with open(output_predict, "w") as f:
+        json.dump(annotations, f, indent=2)
+    return output_predict

@@ -2,7 +2,8 @@
 ClipRange, PromptObj and PromptInfo with the reference's fields (utils.py:10-38), the two list helpers and
 mask_to_bbox (utils.py:156-165).  The plotting helpers and the prompt generation from ground truth
 (mask_to_masks: cv2 closing + connected components, mask_to_points) are not restated: cv2 / matplotlib /
-natsort are not dependencies of this package (see eval/inference.py)."""
+natsort are not dependencies of this package (see eval/inference.py).  mask_to_bbox also serves the threshold
+tuning's host path (eval/export_predict_from_probs.py; the tuning itself is eval/tune_threshold.py)."""
 from __future__ import annotations
 
 from dataclasses import dataclass

@@ -10,6 +10,7 @@ import contextlib
 import math
 import os
 
+import numpy as np
 import torch
 
 from ._lib import call, lib
@@ -1254,12 +1255,61 @@ def rle_words(H, W):
     return (int(H) * int(W) + 63) // 64
 
 
-def mask_export(low, H, W, cat_off, cat_obj, ncat, non_overlap=False, bits=None, scores=None):
+SWEEP_MAX_K = 64  # cuts per s2h_mask_sweep call (csrc/sweep_hist.h)
+
+
+def pack_mask_bits(masks):
+    """bool [ncat, H, W] (numpy, or anything np.asarray takes) -> int64 [ncat, ceil(H W / 64)] numpy: the
+    uint64 words of the column-major bit masks, bit j % 64 of word j // 64 = pixel (j % H, j // H) -- the
+    layout s2h_mask_export writes and s2h_mask_sweep reads as ground truth.  Host numpy; unused tail bits 0."""
+    m = np.asarray(masks).astype(bool)
+    assert m.ndim == 3, "masks must be [ncat, H, W]"
+    ncat, H, W = m.shape
+    nw = rle_words(H, W)
+    flat = np.zeros((ncat, nw * 64), dtype=bool)
+    flat[:, :H * W] = m.transpose(0, 2, 1).reshape(ncat, H * W)
+    words = np.packbits(flat.reshape(ncat, nw, 64), axis=2, bitorder="little").view("<u8").reshape(ncat, nw)
+    return words.view(np.int64)
+
+
+def mask_sweep(low, H, W, cat_off, cat_obj, ncat, cuts, gt_bits=None, non_overlap=False, hist=None):
+    """the threshold sweep of one frame (s2h_mask_sweep).  low, cat_off, cat_obj, ncat, non_overlap as for
+    mask_export; cuts [K] fp32 on the device, non-decreasing, 1 <= K <= 64 (eval/tune_threshold.py logit_cuts);
+    gt_bits [ncat, ceil(H W / 64)] int64 on the device (pack_mask_bits) or None = all background.
+    -> hist [ncat, 2, K + 1] int32 (overwritten): hist[c][g][b] = pixels of category c with ground-truth bit g
+    whose merged value m has b = #{k : m >= cuts[k]}.  No scratch; capturable."""
+    assert low.dim() == 3 and low.dtype == torch.float32 and low.is_contiguous()
+    assert cat_off.dtype == torch.int32 and cat_obj.dtype == torch.int32 and cat_off.numel() == ncat + 1
+    assert cat_off.is_contiguous() and cat_obj.is_contiguous()
+    assert cuts.dim() == 1 and cuts.dtype == torch.float32 and cuts.is_contiguous()
+    K = cuts.numel()
+    assert 1 <= K <= SWEEP_MAX_K, f"1 <= K <= {SWEEP_MAX_K} cuts, got {K}"
+    _dev(low, cat_off, cat_obj, cuts)
+    N, hi, wi = low.shape
+    H, W = int(H), int(W)
+    if gt_bits is not None:
+        assert gt_bits.shape == (ncat, rle_words(H, W)) and gt_bits.dtype == torch.int64 and gt_bits.is_contiguous()
+        _dev(gt_bits)
+    if hist is None:
+        hist = torch.empty(ncat, 2, K + 1, device=low.device, dtype=torch.int32)
+    assert hist.numel() == ncat * 2 * (K + 1) and hist.dtype == torch.int32 and hist.is_contiguous()
+    _dev(hist)
+    call("s2h_mask_sweep", N, hi, wi, H, W, ptr(low), ncat, ptr(cat_off), ptr(cat_obj), int(bool(non_overlap)),
+         K, ptr(cuts), None if gt_bits is None else ptr(gt_bits), ptr(hist), stream())
+    return hist
+
+
+def mask_export(low, H, W, cat_off, cat_obj, ncat, non_overlap=False, bits=None, scores=None, cut=None, vmax=None):
     """category-merged bit masks and per-object scores of one frame (s2h_mask_export).  low [N, hi, wi] fp32
     contiguous low-res logits; cat_off [ncat + 1] / cat_obj int32: the object -> category CSR.
     -> (bits [ncat, ceil(H W / 64)] int64 holding the uint64 words of the column-major masks, bit j = pixel
     (j % H, j // H); scores [N] fp32 = mean sigmoid of the video-resolution logits).  The scratch comes from
-    the torch allocator, so the call can be captured in a HIP graph."""
+    the torch allocator, so the call can be captured in a HIP graph.
+    cut (a float; s2h_mask_export_cut): foreground is value >= cut instead of value > 0, and the result is
+    (bits, scores, vmax [N] fp32 = each object's maximum video-resolution value)."""
+    if cut is not None:
+        return _mask_export_cut(low, H, W, cat_off, cat_obj, ncat, non_overlap, bits, scores, float(cut), vmax)
+    assert vmax is None, "vmax is an output of mask_export(cut=...)"
     assert low.dim() == 3 and low.dtype == torch.float32 and low.is_contiguous()
     assert cat_off.dtype == torch.int32 and cat_obj.dtype == torch.int32 and cat_off.numel() == ncat + 1
     assert cat_off.is_contiguous() and cat_obj.is_contiguous()
@@ -1278,6 +1328,31 @@ def mask_export(low, H, W, cat_off, cat_obj, ncat, non_overlap=False, bits=None,
     call("s2h_mask_export", N, hi, wi, H, W, ptr(low), ncat, ptr(cat_off), ptr(cat_obj), int(bool(non_overlap)),
          ptr(bits), ptr(scores), ptr(work), stream())
     return bits, scores
+
+
+def _mask_export_cut(low, H, W, cat_off, cat_obj, ncat, non_overlap, bits, scores, cut, vmax):
+    assert low.dim() == 3 and low.dtype == torch.float32 and low.is_contiguous()
+    assert cat_off.dtype == torch.int32 and cat_obj.dtype == torch.int32 and cat_off.numel() == ncat + 1
+    assert cat_off.is_contiguous() and cat_obj.is_contiguous()
+    assert cut == cut, "cut must not be NaN"
+    _dev(low, cat_off, cat_obj)
+    N, hi, wi = low.shape
+    H, W = int(H), int(W)
+    nw = rle_words(H, W)
+    if bits is None:
+        bits = torch.empty(ncat, nw, device=low.device, dtype=torch.int64)
+    if scores is None:
+        scores = torch.empty(N, device=low.device, dtype=torch.float32)
+    if vmax is None:
+        vmax = torch.empty(N, device=low.device, dtype=torch.float32)
+    assert bits.shape == (ncat, nw) and bits.dtype == torch.int64 and bits.is_contiguous()
+    assert scores.numel() == N and scores.dtype == torch.float32 and scores.is_contiguous()
+    assert vmax.numel() == N and vmax.dtype == torch.float32 and vmax.is_contiguous()
+    _dev(bits, scores, vmax)
+    work = torch.empty(max(1, 2 * N * ((H * W + 255) // 256)), device=low.device, dtype=torch.float32)
+    call("s2h_mask_export_cut", N, hi, wi, H, W, ptr(low), ncat, ptr(cat_off), ptr(cat_obj), int(bool(non_overlap)),
+         cut, ptr(bits), ptr(scores), ptr(vmax), ptr(work), stream())
+    return bits, scores, vmax
 
 
 def rle_transitions(bits, H, W, capacity=None, hdr=None, trans=None):

@@ -23,7 +23,9 @@ published SAM2.1 algorithm (sam2/sam2_video_predictor.py):
     heads and the bilinear upsampling; `postprocess_on_device=False` keeps the host scipy path for A/B;
   * `propagate_in_video_export` is the same tracking loop feeding the evaluation's predict.json
     (eval/inference.py): per frame a MergedFrame -- category-merged COCO RLE run boundaries, area, box and
-    per-object scores from csrc/rle.hip -- instead of video-resolution logits.
+    per-object scores from csrc/rle.hip -- instead of video-resolution logits; with `threshold=` the masks
+    are cut at a tuned probability threshold, with `sweep_cuts=` the frame also carries the histogram that
+    tunes it (eval/tune_threshold.py), in the same single copy.
 
 MI355X-first choices (not observable in the outputs): objects whose conditioning / tracked frame
 sets agree are run as ONE batch through the kernels instead of one object at a time (each object
@@ -152,16 +154,31 @@ class MergedFrame:
     the frame uses of it (656 KB at 1024 x 1280 and 4 categories, of which ~96 KB are typically positions):
     copying only the used part would need the header on the host first, a second round trip per frame."""
 
-    def __init__(self, low, H, W, obj_ids, cat_ids, cat_off, cat_obj, non_overlap=False, capacity=None, pool=None):
+    def __init__(self, low, H, W, obj_ids, cat_ids, cat_off, cat_obj, non_overlap=False, capacity=None, pool=None,
+                 cut=None, sweep_cuts=None, gt_bits=None, obj_cats=None):
         ncat, N = len(cat_ids), low.shape[0]
+        self.obj_cats = None if obj_cats is None else list(obj_cats)  # the category of every object
         self.low_res_logits = low  # [N, h, w] fp32 (what a probability dump upsamples)
         self.height, self.width, self.obj_ids, self.cat_ids = int(H), int(W), list(obj_ids), list(cat_ids)
         self.capacity = int(capacity) if capacity is not None else max(4096, 32 * self.width * ncat)
+        self.cut = None if cut is None else float(cut)
+        self.sweep_bins = 0 if sweep_cuts is None else sweep_cuts.numel() + 1
+        # one buffer, one copy: header | scores | max logits (cut) | sweep histogram (sweep_cuts) | run boundaries
         n_hdr = ncat * ops.RLE_HDR
-        buf = torch.empty(n_hdr + N + self.capacity, device=low.device, dtype=torch.int32)
-        self.bits, _ = ops.mask_export(low, H, W, cat_off, cat_obj, ncat, non_overlap,
-                                       scores=buf[n_hdr:n_hdr + N].view(torch.float32))
-        ops.rle_transitions(self.bits, H, W, hdr=buf[:n_hdr], trans=buf[n_hdr + N:])
+        n_max = N if self.cut is not None else 0
+        n_hist = ncat * 2 * self.sweep_bins
+        self._fixed = n_hdr + N + n_max + n_hist
+        buf = torch.empty(self._fixed + self.capacity, device=low.device, dtype=torch.int32)
+        scores = buf[n_hdr:n_hdr + N].view(torch.float32)
+        if self.cut is None:
+            self.bits, _ = ops.mask_export(low, H, W, cat_off, cat_obj, ncat, non_overlap, scores=scores)
+        else:
+            self.bits, _, _ = ops.mask_export(low, H, W, cat_off, cat_obj, ncat, non_overlap, scores=scores, cut=self.cut,
+                                              vmax=buf[n_hdr + N:n_hdr + N + n_max].view(torch.float32))
+        if n_hist:
+            ops.mask_sweep(low, H, W, cat_off, cat_obj, ncat, sweep_cuts, gt_bits, non_overlap,
+                           hist=buf[n_hdr + N + n_max:self._fixed])
+        ops.rle_transitions(self.bits, H, W, hdr=buf[:n_hdr], trans=buf[self._fixed:])
         self._pool = pool if pool is not None else StagingPool()
         self.staging, self.event = self._pool.take(buf.numel())
         self.staging.copy_(buf, non_blocking=True)
@@ -172,7 +189,10 @@ class MergedFrame:
     def result(self):
         """{"categories": {cat_id: {"segmentation": {"size": [H, W], "counts": str}, "bbox": [xmin, ymin,
         xmax, ymax] (floats, the reference's mask_to_bbox corners), "area": int}} for the non-empty
-        categories in first-seen order of the objects, "scores": {obj_id: float}}"""
+        categories in first-seen order of the objects, "scores": {obj_id: float}}; with a cut also "max_logit":
+        {obj_id: float}, the maximum video-resolution logit of each object (and "obj_cats": {obj_id:
+        category}); with sweep cuts also "cat_ids" and "sweep": int32 [ncat, 2, K + 1] in `cat_ids` order
+        (empty categories included), the counts of s2h_mask_sweep"""
         if self._result is not None:
             return self._result
         from .data import rle
@@ -182,7 +202,7 @@ class MergedFrame:
         n_hdr = ncat * ops.RLE_HDR
         hdr = a[:n_hdr].reshape(ncat, ops.RLE_HDR)
         scores = a[n_hdr:n_hdr + N].view(np.float32)
-        trans = a[n_hdr + N:]
+        trans = a[self._fixed:]
         if ncat and int(hdr[0, 7]) > self.capacity:  # overflow: the header says how much room is needed
             # (the bits were written on the stream of __init__, which the event follows: order this stream,
             # whichever it is by now, behind it)
@@ -199,6 +219,15 @@ class MergedFrame:
                          "bbox": [float(xmin), float(ymin), float(xmax), float(ymax)], "area": area}
         self._result = {"categories": cats,
                         "scores": OrderedDict((i, float(v)) for i, v in zip(self.obj_ids, scores))}
+        if self.cut is not None:
+            vmax = a[n_hdr + N:n_hdr + 2 * N].view(np.float32)
+            self._result["max_logit"] = OrderedDict((i, float(v)) for i, v in zip(self.obj_ids, vmax))
+            if self.obj_cats is not None:
+                self._result["obj_cats"] = OrderedDict(zip(self.obj_ids, self.obj_cats))
+        if self.sweep_bins:
+            n_hist = ncat * 2 * self.sweep_bins
+            self._result["cat_ids"] = list(self.cat_ids)
+            self._result["sweep"] = a[self._fixed - n_hist:self._fixed].reshape(ncat, 2, self.sweep_bins).copy()
         self.runs_total = int(hdr[0, 7]) if ncat else 0
         # everything is decoded into Python objects: the block goes back to the pool for the next frame
         self._pool.give(a.size, (self.staging, self.event))
@@ -571,20 +600,40 @@ class SAM2VideoPredictor:
 
     @torch.no_grad()
     def propagate_in_video_export(self, inference_state, obj_to_cat, start_frame_idx=None,
-                                  max_frame_num_to_track=None, reverse=False):
+                                  max_frame_num_to_track=None, reverse=False, threshold=None, sweep_cuts=None,
+                                  gt_bits=None):
         """propagate_in_video for the evaluation's export (reference eval/inference.py:487-514 + :870-901):
         the same tracking, but instead of [N, 1, H, W] logits every frame yields
         (frame_idx, obj_ids, MergedFrame): the objects' masks OR-ed per category (`obj_to_cat`: a dict or a
         callable obj_id -> category id), as COCO RLE run boundaries with area, bounding box and the
         per-object scores, computed by csrc/rle.hip from the low-res logits on the current stream
         (`non_overlap_masks` honoured).  The video-resolution logits are never stored and nothing here waits
-        for the device: MergedFrame.result() does, when the caller asks."""
+        for the device: MergedFrame.result() does, when the caller asks.
+
+        threshold (a probability in (0, 1]): the masks are binarised as the reference thresholds its float16
+        dump, `float16(sigmoid(v)) >= float16(threshold)`, which is v >= cut(threshold)
+        (eval/tune_threshold.py logit_cuts); result() gains "max_logit".  sweep_cuts (K <= 64 non-decreasing
+        float32 logit cuts) with gt_bits (a callable frame_idx -> device int64 [ncat, ceil(H W / 64)] in the
+        first-seen category order of the objects, or None = no ground truth): result() gains "sweep", the
+        per-category histogram of s2h_mask_sweep, in the same buffer and the same single copy."""
         s = inference_state
+        cut = None
+        if threshold is not None:
+            from .eval.tune_threshold import logit_cuts
+            cut = float(logit_cuts([threshold])[0])
+        if sweep_cuts is not None and not isinstance(sweep_cuts, torch.Tensor):  # uploaded once per state
+            host = np.ascontiguousarray(sweep_cuts, dtype=np.float32)
+            key = ("sweep_cuts", host.tobytes())
+            if key not in s["constants"]:
+                s["constants"][key] = torch.from_numpy(host).to(s["device"])
+            sweep_cuts = s["constants"][key]
         for t, masks in self._propagate(s, start_frame_idx, max_frame_num_to_track, reverse):
-            yield t, s["obj_ids"], self._export_frame(s, masks, obj_to_cat)
+            gt = gt_bits(t) if (sweep_cuts is not None and gt_bits is not None) else None
+            yield t, s["obj_ids"], self._export_frame(s, masks, obj_to_cat, cut, sweep_cuts, gt)
 
     def _export_csr(self, s, obj_to_cat):
-        """(category ids in first-seen order of the objects, cat_off, cat_obj on the device)"""
+        """(category ids in first-seen order of the objects, cat_off, cat_obj on the device, the category of
+        every object)"""
         ids = list(s["obj_ids"])
         cats = [obj_to_cat(i) if callable(obj_to_cat) else obj_to_cat[i] for i in ids]
         key = ("export_csr", tuple(ids), tuple(cats))
@@ -595,17 +644,18 @@ class SAM2VideoPredictor:
             off = np.cumsum([0] + [len(m) for m in members]).astype(np.int32)
             obj = np.asarray([k for m in members for k in m] + [0], dtype=np.int32)  # (never empty)
             c = s["constants"][key] = (order, torch.from_numpy(off).to(s["device"]),
-                                       torch.from_numpy(obj).to(s["device"]))
+                                       torch.from_numpy(obj).to(s["device"]), cats)
         return c
 
-    def _export_frame(self, s, masks, obj_to_cat):
+    def _export_frame(self, s, masks, obj_to_cat, cut=None, sweep_cuts=None, gt_bits=None):
         """low-res logits [N, 1, h, w] of a frame -> MergedFrame (kernels and the copy enqueued, not waited for)"""
-        cat_ids, cat_off, cat_obj = self._export_csr(s, obj_to_cat)
+        cat_ids, cat_off, cat_obj, obj_cats = self._export_csr(s, obj_to_cat)
         N, _, h, w = masks.shape
         H, W = s["video_height"], s["video_width"]
         low = masks.reshape(N, h, w).contiguous()
         return MergedFrame(low, H, W, list(s["obj_ids"]), cat_ids, cat_off, cat_obj,
-                           self.non_overlap_masks and N > 1, pool=s["export_staging"])
+                           self.non_overlap_masks and N > 1, pool=s["export_staging"], cut=cut,
+                           sweep_cuts=sweep_cuts, gt_bits=gt_bits, obj_cats=obj_cats)
 
     def _propagate(self, inference_state, start_frame_idx, max_frame_num_to_track, reverse):
         """the tracking loop both generators share -> (frame_idx, low-res logits [N, 1, 4h, 4w])"""
