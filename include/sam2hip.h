@@ -633,6 +633,49 @@ int s2h_cc_label(int N, int H, int W, const float* scores, int positive, int* la
  * scratch; out must not alias scores; max_area >= 1; sizes as for s2h_cc_label. */
 int s2h_fill_holes(int N, int H, int W, const float* scores, int max_area, float* out, int* work,
                    hipStream_t st);
+/* s2h_cc_label on byte masks [N, H, W]: foreground is mask != 0 when `positive`, mask == 0 otherwise; the same
+ * kernels, so labels and areas are those of s2h_cc_label on the corresponding 0 / 1 scores. */
+int s2h_cc_label_u8(int N, int H, int W, const uint8_t* mask, int positive, int* labels, int* areas,
+                    hipStream_t st);
+/* ---- prompts from ground truth (reference sam2_video/eval/inference.py:275-326 get_each_obj, eval/utils.py:95-153
+ * mask_to_masks / mask_to_points; csrc/gtprompt.hip).  Common to the five entries below: pure functions of their
+ * inputs, integer arithmetic and integer atomics only, every device loop bounded independently of the data, no
+ * host round trip; H, W >= 1, H * W <= 2^24, N * H * W < 2^31 - 256 (A in place of N for s2h_rle_decode).
+ *
+ * COCO RLE -> byte masks (pycocotools mask.decode).  run_end[run_off[a] .. run_off[a + 1]) = the cumulative sums
+ * of annotation a's counts: ascending, the last one H W; positions are column-major.  mask [A, H, W] uint8,
+ * row-major: pixel (y, x) = k & 1 with k the index of the first run_end > x H + y within the annotation (the
+ * number of its runs when there is none).  A zero-length first run (the mask starts set) and a single run (an
+ * empty mask) are valid; run_off [A + 1] ascending from 0. */
+int s2h_rle_decode(int A, int H, int W, const int* run_off, const int* run_end, uint8_t* mask, hipStream_t st);
+/* Rectangular dilation (op 0) or erosion (op 1) of byte masks [N, H, W] (nonzero = set; out is 0 / 1):
+ * out(y, x) = OR resp. AND of in(y + dy, x + dx) over dy in [y_lo, y_hi], dx in [x_lo, x_hi], restricted to the
+ * positions inside the image -- outside pixels are ignored by both, cv2's default morphology border.
+ * -32 <= lo <= 0 <= hi <= 32.  Two separable passes; work: N H W bytes of scratch; in, out and work are three
+ * different buffers. */
+int s2h_morph_rect(int N, int H, int W, const uint8_t* in, int op, int y_lo, int y_hi, int x_lo, int x_hi,
+                   uint8_t* out, uint8_t* work, hipStream_t st);
+/* The components of area >= min_area of images labelled by s2h_cc_label(_u8) (labels, areas as it writes them),
+ * per image in ascending order of root index = raster order of the first pixel (cv2.connectedComponentsWithStats'
+ * order), the images back to back.  grid: [H, W] uint8 or NULL; a pixel of a component is "selected" when
+ * grid is NULL or nonzero there.  stats [capacity, 9] int64 per kept component: root label, area, xmin, ymin,
+ * xmax, ymax (inclusive, of all its pixels), n_sel, sum x and sum y over its selected pixels.
+ * hdr [2 N + 2] int32: count and offset per image, then the total, then a status word: 1 when an image has more
+ * than 255 kept components (the index image then saturates at 255 there and must not be used), else 0.  When
+ * total > capacity only the first `capacity` rows are written (nothing past the end); the header is complete
+ * either way.  index [N, H, W] uint8: 0 = not in a kept component, i = the i-th kept component of its image.
+ * work: N H W + N ceil(H W / 256) int32 of scratch.  Additionally N ceil(H W / 256) < 2^31. */
+int s2h_cc_components(int N, int H, int W, const int* labels, const int* areas, int min_area, const uint8_t* grid,
+                      int capacity, int* hdr, int64_t* stats, uint8_t* index, int* work, hipStream_t st);
+/* The q_rank[q]-th pixel, in row-major order, of image q_img[q] among the pixels with
+ * (labels == q_label[q]) != (q_neg[q] != 0) that also lie on the grid ([H, W] uint8, NULL = every pixel):
+ * np.argwhere(mask & GRID)[rank] of eval/utils.py mask_to_points, for the component (q_neg 0) or its
+ * complement (q_neg 1).  xy [Q, 2] int32 = (x, y), (-1, -1) when the rank is negative or not below the count;
+ * count [Q] int32 = the number of such pixels (0 for an image index outside [0, N)).
+ * work: Q ceil(H W / 4096) int32 of scratch, and Q ceil(H W / 4096) < 2^31. */
+int s2h_mask_rank_select(int Q, const int* q_img, const int* q_label, const int* q_neg, const int* q_rank, int N,
+                         int H, int W, const int* labels, const uint8_t* grid, int* xy, int* count, int* work,
+                         hipStream_t st);
 /* Category-merged masks of a tracked frame, bit-packed, without materialising the [N, H, W] logits
  * (reference sam2_video/eval/inference.py:487-514, per object `(out_mask_logits[i] > 0.0).cpu().numpy()` and
  * `torch.sigmoid(out_mask_logits[i]).mean().item()`, and :870-886, the `key % MOD` OR on the host).

@@ -19,12 +19,16 @@ namespace {
 
 // L[i] = -1 off the foreground, else the in-image index of the first pixel of i's run within the wave;
 // cnt[i] = 0
-__global__ __launch_bounds__(256) void cc_init_kernel(int total, int HW, int W, const float* scores, int positive,
-                                                      int* L, int* cnt) {
+// (T = float: a score, cc_fg; T = uint8_t: a mask byte, foreground is != 0, or == 0 when not `positive`)
+__device__ __forceinline__ bool cc_fg_of(float s, int positive) { return cc_fg(s, positive); }
+__device__ __forceinline__ bool cc_fg_of(uint8_t s, int positive) { return (s != 0) == (positive != 0); }
+template <typename T>
+__global__ __launch_bounds__(256) void cc_init_kernel(int total, int HW, int W, const T* scores, int positive, int* L,
+                                                      int* cnt) {
   const int i = blockIdx.x * 256 + threadIdx.x;  // (the host checked total + 256 < 2^31)
   const int lane = threadIdx.x & 63;
   const bool in = i < total;
-  const bool fg = in && cc_fg(scores[in ? i : 0], positive);
+  const bool fg = in && cc_fg_of(scores[in ? i : 0], positive);
   const int q = in ? i % HW : 0;
   const int x = q % W;
   const uint64_t fgm = __ballot(fg);
@@ -109,9 +113,10 @@ int cc_total(int N, int H, int W) {
 }
 
 // steps 1-3: parents flattened to roots in L, component sizes in cnt at the roots
-void cc_roots(int total, int H, int W, const float* scores, int positive, int* L, int* cnt, hipStream_t st) {
+template <typename T>
+void cc_roots(int total, int H, int W, const T* scores, int positive, int* L, int* cnt, hipStream_t st) {
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  hipLaunchKernelGGL(cc_init_kernel, grid, block, 0, st, total, H * W, W, scores, positive, L, cnt);
+  hipLaunchKernelGGL(cc_init_kernel<T>, grid, block, 0, st, total, H * W, W, scores, positive, L, cnt);
   hipLaunchKernelGGL(cc_merge_kernel, grid, block, 0, st, total, H, W, L);
   hipLaunchKernelGGL(cc_flatten_kernel, grid, block, 0, st, total, H * W, L, cnt);
 }
@@ -125,6 +130,18 @@ extern "C" int s2h_cc_label(int N, int H, int W, const float* scores, int positi
   if (total == 0) return 0;
   if (!scores || !labels || !areas) return (int)hipErrorInvalidValue;
   cc_roots(total, H, W, scores, positive, labels, areas, st);
+  hipLaunchKernelGGL(cc_labels_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, H * W, labels,
+                     areas);
+  S2H_LAUNCH_CHECK();
+}
+
+extern "C" int s2h_cc_label_u8(int N, int H, int W, const uint8_t* mask, int positive, int* labels, int* areas,
+                               hipStream_t st) {
+  const int total = cc_total(N, H, W);
+  if (total < 0) return (int)hipErrorInvalidValue;
+  if (total == 0) return 0;
+  if (!mask || !labels || !areas) return (int)hipErrorInvalidValue;
+  cc_roots(total, H, W, mask, positive, labels, areas, st);
   hipLaunchKernelGGL(cc_labels_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, H * W, labels,
                      areas);
   S2H_LAUNCH_CHECK();

@@ -112,3 +112,75 @@ def evaluate_clip(merged_frames: List[Dict], target_masks: torch.Tensor, cat_ids
     P = int(target_masks[0, 0].numel())
     frames = [image_scores_from_counts(counts[t], P, cat_ids) for t in range(T)]
     return get_video_scores_from_frames(frames, cat_ids)
+
+
+# ------------------------------------------------------------------ offline scoring (host, numpy)
+def _merged_counts(anns_dt, anns_gt):
+    """|p & g|, |p | g|, |p|, |g| and the pixel count of the OR-ed masks of one category (eval.py:88-103)"""
+    from ..data import rle
+    dt = merge_masks([rle.decode(a["segmentation"]) for a in anns_dt])
+    gt = merge_masks([rle.decode(a["segmentation"]) for a in anns_gt])
+    if dt is None:
+        dt = np.zeros_like(gt)
+    if gt is None:
+        gt = np.zeros_like(dt)
+    p, g = dt.astype(bool), gt.astype(bool)
+    return [int((p & g).sum()), int((p | g).sum()), int(p.sum()), int(g.sum())], p.size
+
+
+def eval(predict_path, coco_path, output_path, remove_background=False):  # noqa: A001 (the reference's name)
+    """eval.py:53-277 without pycocotools: score `predict_path` (the annotation list inference() writes) against
+    the ground-truth COCO file and write `<output_path>/eval.pkl` -- {"videos": [{"video_id", "frames": [{"video_id",
+    "order_in_video", "cat_scores", "avg_scores"}], "cat_scores", "avg_scores"}], "cat_scores", "avg_scores"} with
+    iou / mae / dice per category id of the ground-truth file (without 0 when remove_background).  -> the result.
+
+    Only images whose is_det_keyframe is not False are scored.  Per category the annotations of each side are
+    OR-ed (data/rle.py decodes them); a category with no annotation on either side is skipped (NaN, ignored by
+    the nanmeans); the four counts go through image_scores_from_counts, whose closed forms are caculate_iou /
+    caculate_dice / caculate_mae on the uint8 masks.  (One corner differs: annotations that exist on both sides
+    but are all empty score NaN here and 0 in the reference; neither inference() nor a COCO export writes empty
+    masks.)  Videos are listed in first-seen order (the reference iterates a set).  Host numpy throughout."""
+    import json
+    import os
+    import pickle
+    with open(coco_path, "r") as f:
+        gt = json.load(f)
+    with open(predict_path, "r") as f:
+        predictions = json.load(f)
+    if isinstance(predictions, dict):
+        predictions = predictions.get("annotations", [])
+    cat_ids = [c["id"] for c in gt.get("categories", [])]
+    if remove_background:
+        cat_ids.remove(0)
+    by_image = {"dt": {}, "gt": {}}
+    for side, anns in (("dt", predictions), ("gt", gt.get("annotations", []))):
+        for a in anns:
+            by_image[side].setdefault(a["image_id"], []).append(a)
+    img_scores: List[Dict] = []
+    for img in gt.get("images", []):
+        if img.get("is_det_keyframe") is False:
+            continue
+        anns_dt, anns_gt = by_image["dt"].get(img["id"], []), by_image["gt"].get(img["id"], [])
+        counts, num_pixels = [], int(img.get("height", 0)) * int(img.get("width", 0))
+        for c in cat_ids:
+            c_dt = [a for a in anns_dt if a["category_id"] == c]
+            c_gt = [a for a in anns_gt if a["category_id"] == c]
+            if not c_dt and not c_gt:
+                counts.append([0, 0, 0, 0])
+                continue
+            row, num_pixels = _merged_counts(c_dt, c_gt)
+            counts.append(row)
+        score = {"video_id": img["video_id"], "order_in_video": img["order_in_video"]}
+        score.update(image_scores_from_counts(np.asarray(counts, dtype=np.int64).reshape(-1, 4), max(num_pixels, 1),
+                                              cat_ids))
+        img_scores.append(score)
+    video_scores = []
+    for video_id in dict.fromkeys(s["video_id"] for s in img_scores):
+        video = {"video_id": video_id}
+        video.update(get_video_scores_from_frames([s for s in img_scores if s["video_id"] == video_id], cat_ids))
+        video_scores.append(video)
+    result = get_result(video_scores, cat_ids)
+    os.makedirs(str(output_path), exist_ok=True)
+    with open(f"{output_path}/eval.pkl", "wb") as f:
+        pickle.dump(result, f)
+    return result

@@ -23,23 +23,39 @@ that tune_threshold.grid_search reloads per threshold -- and `threshold=` + save
 export_predict_from_probs.py's `predict_t0.xx.json` at the tuned threshold.  `probs_out_dir` and the two host
 modules stay as the A/B path.
 
-Out of scope: generating the prompts from ground truth (get_each_obj / generate_prompts_by_*: utils.py
-mask_to_masks is cv2.morphologyEx + cv2.connectedComponentsWithStats, and cv2 is not a dependency -- a scipy
-restatement could not be pinned against it) and the top-level `inference()` that drives it from a COCO file.
-Callers build PromptInfo lists themselves (eval/utils.py) and call process_video_clip + save_as_coco_format.
+Prompts from ground truth and the driver: get_each_obj (:275-326), find_prompt_frame (:147-175),
+generate_prompts_by_clip_length / _by_categories (:598-703), merge_prompts (:706-767), process_singel_video,
+process_all_videos (:771-841) and inference() (:919-1085) over a CocoIndex (no pycocotools).  With
+`on_device=True` get_each_obj runs a prompt frame's annotations as one batch through csrc/gtprompt.hip and
+csrc/cc.hip -- RLE decode, the 10 x 10 closing, labelling, the kept components with their boxes and centre sums,
+and the pixel of every drawn rank -- with two copies to the host; the random draws are the reference's
+np.random.choice calls in the reference's order, so both paths give the same prompts under the same seed.
+`on_device=False` is eval/utils.py mask_to_masks / mask_to_points, the A/B path.  The closing's window is
+eval/utils.py CLOSE_DILATE_WINDOW: it follows OpenCV's documented formulas and was not checked against an
+OpenCV binary.
+
+Out of scope: PromptObjNoiseAdder (`noised_prompt=True` raises: it needs albumentations) and the reference's
+dead helpers generate_negative_samples, fluctuate_point and get_obj_from_masks.
 """
 from __future__ import annotations
 
 import json
 import os
 import pickle
-from typing import Dict, List, Optional
+from dataclasses import dataclass
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from ..data import rle
+from . import utils as _utils
 from .utils import ClipRange, PromptInfo, PromptObj, mask_to_bbox, sort_dicts_by_field
+
+# what inference() builds when no predictor is passed (the reference's module globals model_cfg / sam2_checkpoint;
+# its checkpoint path is site-specific, so the default here is the builder's own)
+MODEL_CFG = "sam2_hiera_t.yaml"
+SAM2_CHECKPOINT = None
 
 # train-time prompt names -> the names add_prompt switches on (inference.py:1004-1010)
 PROMPT_TYPES = {"point": "points", "box": "bbox", "mask": "mask", "points": "points", "bbox": "bbox"}
@@ -291,3 +307,352 @@ def save_thresholded_predict(all_video_segments, frames_by_video, threshold, out
     with open(output_predict, "w") as f:
         json.dump(annotations, f, indent=2)
     return output_predict
+
+
+# ------------------------------------------------------------------------------ prompts from ground truth
+class CocoIndex:
+    """what the driver reads of a COCO file (the pycocotools.COCO calls of the reference): the images, the
+    annotations of an image and the category ids, all in file order; mod = max(category ids) + 1"""
+
+    def __init__(self, coco):
+        if not isinstance(coco, dict):
+            with open(coco, "r") as f:
+                coco = json.load(f)
+        self.dataset = coco
+        self.imgs: List[Dict] = list(coco.get("images", []))
+        self.cat_ids: List[int] = [c["id"] for c in coco.get("categories", [])]
+        self.anns_by_image: Dict = {}
+        for a in coco.get("annotations", []):
+            self.anns_by_image.setdefault(a["image_id"], []).append(a)
+        self.mod = max(self.cat_ids) + 1
+
+    def anns(self, image_id) -> List[Dict]:
+        return self.anns_by_image.get(image_id, [])
+
+    def video_ids(self) -> List:
+        """first-seen order (the reference iterates a set)"""
+        return list(dict.fromkeys(img["video_id"] for img in self.imgs))
+
+    def frames(self, video_id) -> List[Dict]:
+        return _utils.get_dicts_by_field_value(self.imgs, "video_id", video_id)
+
+
+def _draw_ranks(n: int, num_points: int, include_center: bool):
+    """the draws mask_to_points makes on a mask with n (grid-selected) pixels, without the pixels: -> (whether the
+    centre leads the result, the ranks of the sampled pixels in np.argwhere order).  The same early return and
+    the same np.random.choice call on the global generator as eval/utils.py mask_to_points."""
+    if include_center is True:
+        num_points -= 1
+    if num_points > n:
+        return False, np.arange(n, dtype=np.int64)
+    return bool(include_center), np.random.choice(n, num_points, replace=False)
+
+
+def _host_objs(anns, mod, obj_count, num_points, num_neg_points, include_center):
+    objs = []
+    for ann in anns:
+        for mask in _utils.mask_to_masks(rle.decode(ann["segmentation"])):
+            pos = _utils.mask_to_points(mask, num_points=num_points, include_center=include_center)
+            neg = _utils.mask_to_points(np.logical_not(mask), num_points=num_neg_points, include_center=False)
+            objs.append(PromptObj(mask=mask, bbox=mask_to_bbox(mask), points=np.concatenate([pos, neg]),
+                                  obj_id=obj_count * mod + ann["category_id"],
+                                  pos_or_neg_label=np.concatenate([np.ones(len(pos)), np.zeros(len(neg))])))
+            obj_count += 1
+    return objs, obj_count
+
+
+def _device_objs(anns, mod, obj_count, num_points, num_neg_points, include_center, device):
+    from ..kernels import ops
+    counts, size = [], None
+    for ann in anns:
+        seg = rle._as_rle(ann["segmentation"])
+        hw = [int(v) for v in seg["size"]]
+        if size is not None and hw != size:
+            raise ValueError(f"annotations of image {ann.get('image_id')} have sizes {size} and {hw}")
+        size = hw
+        c = seg["counts"]
+        if isinstance(c, bytes):
+            c = c.decode("ascii")
+        counts.append(rle.counts_from_string(c) if isinstance(c, str) else list(c))
+    if not anns:
+        return [], obj_count
+    H, W = size
+    A = len(anns)
+    grid_host = _utils.GRID
+    grid = None
+    if grid_host is not None:
+        if grid_host.shape != (H, W):
+            raise ValueError(f"GRID is {grid_host.shape}, the frame's masks are {(H, W)}")
+        grid = torch.from_numpy(np.ascontiguousarray(grid_host, dtype=np.uint8)).to(device)
+    yw, ew = _utils.CLOSE_DILATE_WINDOW, _utils.CLOSE_ERODE_WINDOW
+    raw = ops.rle_decode(counts, H, W, device=device)
+    closed = ops.morph_rect(ops.morph_rect(raw, "dilate", yw, yw), "erode", ew, ew)
+    labels, areas = ops.cc_label_u8(closed)
+    hdr_d, stats_d, index_d = ops.cc_components(labels, areas, _utils.MIN_COMPONENT_AREA, grid=grid)
+    # header, stats and index image in one copy
+    packed = torch.cat([hdr_d.view(torch.uint8), stats_d.reshape(-1).view(torch.uint8), index_d.reshape(-1)]).cpu().numpy()
+    nh, ns = hdr_d.numel() * 4, stats_d.numel() * 8
+    hdr = packed[:nh].view(np.int32)
+    stats = packed[nh:nh + ns].view(np.int64).reshape(-1, ops.GP_STATS)
+    index = packed[nh + ns:].reshape(A, H, W)
+    if hdr[2 * A + 1] != 0:
+        raise RuntimeError(f"an annotation closes into more than {ops.GP_MAX_INDEX} components of area >= "
+                           f"{_utils.MIN_COMPONENT_AREA}: the uint8 index image cannot name them")
+    n_domain = int(grid_host.sum()) if grid_host is not None else H * W
+    # the host draws, in the reference's order: per component the positives, then the negatives
+    plan, queries = [], []
+    for a, ann in enumerate(anns):
+        cnt, off = int(hdr[2 * a]), int(hdr[2 * a + 1])
+        for j in range(cnt):
+            label, area, xmin, ymin, xmax, ymax, n_sel, sx, sy = (int(v) for v in stats[off + j])
+            use_center, pos_ranks = _draw_ranks(n_sel, num_points, include_center)
+            _, neg_ranks = _draw_ranks(n_domain - n_sel, num_neg_points, False)
+            center = None
+            if use_center:
+                # Sum // n equals the reference's float64 mean truncated: the sums are exact in float64
+                # (< 2^53), and a quotient just below an integer k <= 2^24 is at least 1 / n >= 2^-24 below it,
+                # far more than float64's spacing there, so the division cannot round up to k.
+                center = (np.array([[sx // n_sel, sy // n_sel]], dtype=np.int64) if n_sel > 0 else
+                          np.mean(np.zeros((0, 2), dtype=np.int64), axis=0).astype(int).reshape(1, -1))
+            q0 = len(queries)
+            queries += [(a, label, 0, int(r), n_sel) for r in pos_ranks]
+            queries += [(a, label, 1, int(r), n_domain - n_sel) for r in neg_ranks]
+            plan.append((a, j, ann["category_id"], [xmin, ymin, xmax, ymax], center, q0, len(pos_ranks), len(neg_ranks)))
+    if queries:
+        q = torch.from_numpy(np.asarray([t[:4] for t in queries], dtype=np.int32).T.copy()).to(device)
+        xy_d, count_d = ops.mask_rank_select(q[0], q[1], q[2], q[3], labels, grid=grid)
+        out = torch.cat([xy_d.reshape(-1), count_d]).cpu().numpy()  # the points in one copy
+        xy, count = out[:2 * len(queries)].reshape(-1, 2).astype(np.int64), out[2 * len(queries):]
+        want = np.asarray([t[4] for t in queries])
+        if not np.array_equal(count, want) or (xy < 0).any():
+            raise RuntimeError("s2h_mask_rank_select disagrees with s2h_cc_components about the pixel counts")
+    else:
+        xy = np.zeros((0, 2), dtype=np.int64)
+    objs = []
+    for a, j, cat, box, center, q0, n_pos, n_neg in plan:
+        pos = xy[q0:q0 + n_pos]
+        if center is not None:
+            pos = np.concatenate([center, pos], axis=0)
+        neg = xy[q0 + n_pos:q0 + n_pos + n_neg]
+        objs.append(PromptObj(mask=index[a] == j + 1, bbox=[float(v) for v in box], points=np.concatenate([pos, neg]),
+                              obj_id=obj_count * mod + cat,
+                              pos_or_neg_label=np.concatenate([np.ones(len(pos)), np.zeros(len(neg))])))
+        obj_count += 1
+    return objs, obj_count
+
+
+def get_each_obj(coco: CocoIndex, prompt_frame, *, mod, obj_count, num_points, num_neg_points, include_center,
+                 cats=None, on_device: bool = True, device="cuda") -> Tuple[List[PromptObj], int]:
+    """inference.py:275-326 with its globals as arguments: every annotation of the frame (of the categories
+    `cats` when given) is closed and split into its components of area >= 10 (mask_to_masks), and every
+    component becomes a PromptObj -- mask (host bool [H, W] of the closed component), bbox [xmin, ymin, xmax,
+    ymax] floats, points int64 [k, 2] (x, y): the positives (centre first when include_center) then the
+    negatives, pos_or_neg_label float64 ones then zeros, obj_id = obj_count * mod + category_id with obj_count
+    incremented per component.  -> (objs, the new obj_count).
+
+    on_device: the frame's annotations as one batch through the HIP kernels (module docstring), two copies to the
+    host; the random stream is the reference's: per component np.random.choice(n_sel, k, replace=False) for the
+    positives, then np.random.choice(n_neg, num_neg_points, replace=False) for the negatives, on the global numpy
+    generator, with mask_to_points' early returns -- so both paths return equal objects under one seed."""
+    anns = [a for a in coco.anns(prompt_frame["id"]) if cats is None or a["category_id"] in cats]
+    if on_device:
+        return _device_objs(anns, mod, obj_count, num_points, num_neg_points, include_center, device)
+    return _host_objs(anns, mod, obj_count, num_points, num_neg_points, include_center)
+
+
+@dataclass
+class PromptGen:
+    """the reference's prompt globals (COCO_INFO, MOD, OBJ_COUNT, NUM_POINTS, NUM_NEG_POINTS, INCLUDE_CENTER) for
+    one run: objs(frame) is get_each_obj(frame) with the running object count"""
+
+    coco: CocoIndex
+    num_points: int = 1
+    num_neg_points: int = 0
+    include_center: bool = True
+    on_device: bool = True
+    device: str = "cuda"
+    obj_count: int = 0
+
+    def objs(self, frame, cats=None) -> List[PromptObj]:
+        objs, self.obj_count = get_each_obj(self.coco, frame, mod=self.coco.mod, obj_count=self.obj_count,
+                                            num_points=self.num_points, num_neg_points=self.num_neg_points,
+                                            include_center=self.include_center, cats=cats, on_device=self.on_device,
+                                            device=self.device)
+        return objs
+
+
+def find_prompt_frame(coco: CocoIndex, frames, clip_range: ClipRange):
+    """the first keyframe (is_det_keyframe is not False) inside the clip that has annotations, or None"""
+    for frame in frames:
+        if frame.get("is_det_keyframe") is False:
+            continue
+        if frame["order_in_video"] < clip_range.start_idx or frame["order_in_video"] > clip_range.end_idx:
+            continue
+        if not coco.anns(frame["id"]):
+            continue
+        return frame
+    return None
+
+
+def _prompt_info(gen: PromptGen, frame, prompt_type) -> PromptInfo:
+    return PromptInfo(prompt_objs=gen.objs(frame), frame_idx=frame["order_in_video"], prompt_type=prompt_type,
+                      video_id=str(frame["video_id"]), path=frame["path"], clip_range=None)
+
+
+def generate_prompts_by_categories(gen: PromptGen, frames, prompt_type: str):
+    """inference.py:598-654: a new clip starts at every keyframe that shows a category not seen before;
+    yields ([PromptInfo], ClipRange)"""
+    existing, prev, prev_start, out = set(), None, None, []
+    for frame in frames:
+        if frame.get("is_det_keyframe") is False:
+            continue
+        frame_cats = {a["category_id"] for a in gen.coco.anns(frame["id"])}
+        if frame_cats.issubset(existing):
+            continue
+        existing |= frame_cats
+        info = _prompt_info(gen, frame, prompt_type)
+        if prev is not None:
+            prev.clip_range = ClipRange(prev_start, info.frame_idx - 1)
+            out.append(([prev], ClipRange(prev_start, info.frame_idx - 1)))
+        prev, prev_start = info, info.frame_idx
+    if prev is not None and prev_start != len(frames) - 1:  # (as the reference: a last clip of one frame is dropped)
+        prev.clip_range = ClipRange(prev_start, len(frames) - 1)
+        out.append(([prev], ClipRange(prev_start, len(frames) - 1)))
+    yield from out
+
+
+def generate_prompts_by_clip_length(gen: PromptGen, frames, prompt_type, clip_length: Optional[int]):
+    """inference.py:657-703: clips of clip_length frames (None: the whole video), each prompted on its first
+    annotated keyframe; a range without one is absorbed into the clip before it; yields ([PromptInfo], ClipRange)"""
+    if clip_length is None:
+        clip_length = len(frames)
+    cur_start, cur_end, cur_prompts = 0, -1, []
+    for start_idx in range(0, len(frames), clip_length):
+        end_idx = min(start_idx + clip_length - 1, len(frames) - 1)
+        prompt_frame = find_prompt_frame(gen.coco, frames, ClipRange(start_idx, end_idx))
+        if prompt_frame is None:
+            cur_end = end_idx
+            continue
+        if cur_start <= cur_end:
+            for p in cur_prompts:
+                p.clip_range = ClipRange(cur_start, cur_end)
+            yield cur_prompts, ClipRange(cur_start, cur_end)
+            cur_prompts = []
+        cur_prompts.append(_prompt_info(gen, prompt_frame, prompt_type))
+        cur_start, cur_end = start_idx, end_idx
+    if cur_start <= cur_end:
+        for p in cur_prompts:
+            p.clip_range = ClipRange(cur_start, cur_end)
+        yield cur_prompts, ClipRange(cur_start, cur_end)
+
+
+def merge_prompts(prompts_by_categories: Iterable, prompts_by_clip_length: Iterable):
+    """inference.py:706-767: the two range lists keyed by start index (a clip-length range replaces a category
+    range with the same start), sorted; a range that starts before the running one ends cuts it short"""
+    ranges = {}
+    for prompts, clip_range in list(prompts_by_categories) + list(prompts_by_clip_length):
+        ranges[clip_range.start_idx] = (prompts, clip_range)
+    merged, cur = [], None  # cur: [start, end, prompts]
+    for prompts, clip_range in sorted(ranges.values(), key=lambda x: x[1].start_idx):
+        if cur is not None:
+            end = clip_range.start_idx - 1 if clip_range.start_idx < cur[1] else cur[1]
+            for p in cur[2]:
+                p.clip_range = ClipRange(cur[0], end)
+            merged.append((cur[2], ClipRange(cur[0], end)))
+        cur = [clip_range.start_idx, clip_range.end_idx, prompts]
+    if cur is not None:
+        for p in cur[2]:
+            p.clip_range = ClipRange(cur[0], cur[1])
+        merged.append((cur[2], ClipRange(cur[0], cur[1])))
+    return merged
+
+
+def process_singel_video(predictor, gen: PromptGen, frames, prompt_type, clip_length: Optional[int] = None,
+                         variable_cats: bool = False, probs_out_dir=None, *, prompt_log: Optional[List] = None,
+                         export_on_device: bool = True, threshold: Optional[float] = None, sweep=None) -> Dict:
+    """inference.py:771-814 (the reference's spelling): the object count restarts, the video's clips are prompted
+    and tracked one after the other on `predictor`; every clip's PromptInfo list is appended to prompt_log"""
+    gen.obj_count = 0
+    if variable_cats:
+        clips = merge_prompts(generate_prompts_by_categories(gen, frames, prompt_type),
+                              generate_prompts_by_clip_length(gen, frames, prompt_type, clip_length))
+    else:
+        clips = generate_prompts_by_clip_length(gen, frames, prompt_type, clip_length)
+    video_segments = {}
+    for clip_prompts, clip_range in clips:
+        if prompt_log is not None:
+            prompt_log.extend(clip_prompts)
+        video_segments.update(process_video_clip(predictor, frames, clip_prompts, clip_range,
+                                                 probs_out_dir=probs_out_dir, mod=gen.coco.mod,
+                                                 export_on_device=export_on_device, threshold=threshold, sweep=sweep))
+    return video_segments
+
+
+def process_all_videos(predictor, gen: PromptGen, prompt_type, clip_length, variable_cats, probs_out_dir=None, *,
+                       prompt_log: Optional[List] = None, export_on_device: bool = True,
+                       threshold: Optional[float] = None, sweep=None) -> Dict:
+    """inference.py:818-841: {video_id: process_singel_video's result}, the videos in first-seen order"""
+    return {video_id: process_singel_video(predictor, gen, gen.coco.frames(video_id), prompt_type, clip_length,
+                                           variable_cats, probs_out_dir=probs_out_dir, prompt_log=prompt_log,
+                                           export_on_device=export_on_device, threshold=threshold, sweep=sweep)
+            for video_id in gen.coco.video_ids()}
+
+
+def inference(coco_path, output_path, prompt_type, save_video_list=None, clip_length=None, variable_cats=False,
+              num_points=1, include_center=True, noised_prompt=False, noise_intensity=0.1,
+              bbox_noise_type="shift_scale", num_neg_points=0, grid_spaceing=None, probs_out_dir: Optional[str] = None,
+              *, run_dir, model_cfg_override: Optional[str] = None, sam2_checkpoint_override: Optional[str] = None,
+              finetuned_state_dict=None, predictor=None, prompts_on_device: bool = True,
+              export_on_device: bool = True, threshold: Optional[float] = None, sweep=None):
+    """inference.py:919-1085: prompts from the ground truth of `coco_path` (a COCO file whose images carry
+    video_id, order_in_video, is_det_keyframe, path, height and width), every video tracked clip by clip,
+    `<run_dir>/eval/predict.json` and `prompt.pkl` written -> (predict path, prompt path).  prompt_type: point |
+    box | mask (or points | bbox); clip_length None = one clip per video; variable_cats: a new clip also starts
+    where a new category appears; grid_spaceing: sample the points on a grid (init_grid on the first image's
+    size; like the reference, None leaves an earlier grid in place); probs_out_dir (relative: under the eval
+    directory): the float16 probability dumps and their meta.json.  `output_path` is unused, as in the reference.
+
+    Beyond the reference: predictor (None: built once with build_sam2_video_predictor from model_cfg_override /
+    sam2_checkpoint_override or the module's MODEL_CFG / SAM2_CHECKPOINT, and reused for every clip);
+    prompts_on_device (get_each_obj on the HIP kernels); export_on_device, threshold, sweep: see predict_on_video.
+
+    Differences from the reference: the predictor is built (and finetuned_state_dict loaded) once, not per clip;
+    the videos are processed in first-seen order (the reference iterates a set); prompt.pkl holds this call's
+    PromptInfo list only (the reference's module global accumulates across calls); noised_prompt=True raises
+    NotImplementedError (PromptObjNoiseAdder needs albumentations and is not restated), so noise_intensity and
+    bbox_noise_type are unused; the dead helpers generate_negative_samples, fluctuate_point and
+    get_obj_from_masks are not restated."""
+    if noised_prompt:
+        raise NotImplementedError("noised_prompt=True needs PromptObjNoiseAdder, which is built on albumentations "
+                                  "and is not part of this package")
+    if run_dir is None or str(run_dir).strip() == "":
+        raise ValueError("inference(): run_dir must be provided and non-empty")
+    eval_dir = os.path.join(str(run_dir), "eval")
+    os.makedirs(eval_dir, exist_ok=True)
+    coco = CocoIndex(coco_path)
+    if grid_spaceing is not None:
+        _utils.init_grid((coco.imgs[0]["height"], coco.imgs[0]["width"]), grid_spaceing)
+    if probs_out_dir is not None:
+        if not os.path.isabs(probs_out_dir):
+            probs_out_dir = os.path.join(eval_dir, probs_out_dir)
+        os.makedirs(probs_out_dir, exist_ok=True)
+    if predictor is None:
+        from ..predictor import build_sam2_video_predictor
+        predictor = build_sam2_video_predictor(model_cfg_override or MODEL_CFG,
+                                               sam2_checkpoint_override or SAM2_CHECKPOINT)
+    if finetuned_state_dict is not None:
+        _load_finetuned_weights_into_predictor(predictor, finetuned_state_dict)
+    device = predictor.model.arena.device
+    gen = PromptGen(coco, num_points=num_points, num_neg_points=num_neg_points, include_center=include_center,
+                    on_device=prompts_on_device, device=device)
+    prompt_log: List[PromptInfo] = []
+    segments = process_all_videos(predictor, gen, PROMPT_TYPES.get(prompt_type, prompt_type), clip_length,
+                                  variable_cats, probs_out_dir=probs_out_dir, prompt_log=prompt_log,
+                                  export_on_device=export_on_device, threshold=threshold, sweep=sweep)
+    frames_by_video = {video_id: coco.frames(video_id) for video_id in coco.video_ids()}
+    paths = save_as_coco_format(segments, frames_by_video, coco.mod, eval_dir, prompt_info=prompt_log,
+                                save_video_list=save_video_list)
+    if probs_out_dir is not None:
+        from .tune_threshold import write_meta
+        write_meta(probs_out_dir, coco.mod)
+    return paths

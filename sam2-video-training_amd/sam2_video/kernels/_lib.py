@@ -127,6 +127,11 @@ SIGNATURES = {
     "s2h_multimask_select": [I, I, I, L, I, P, P, P, P, P, L, I, I, F, F, P, P, P, P, P, P],
     "s2h_cc_label": [I, I, I, P, I, P, P, P],
     "s2h_fill_holes": [I, I, I, P, I, P, P, P],
+    "s2h_cc_label_u8": [I, I, I, P, I, P, P, P],
+    "s2h_rle_decode": [I, I, I, P, P, P, P],
+    "s2h_morph_rect": [I, I, I, P, I, I, I, I, I, P, P, P],
+    "s2h_cc_components": [I, I, I, P, P, I, P, I, P, P, P, P, P],
+    "s2h_mask_rank_select": [I, P, P, P, P, I, I, I, P, P, P, P, P, P],
     "s2h_mask_export": [I, I, I, I, I, P, I, P, P, I, P, P, P, P],
     "s2h_mask_export_cut": [I, I, I, I, I, P, I, P, P, I, F, P, P, P, P, P],
     "s2h_mask_sweep": [I, I, I, I, I, P, I, P, P, I, I, P, P, P, P],

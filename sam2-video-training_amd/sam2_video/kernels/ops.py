@@ -1247,6 +1247,126 @@ def fill_holes(scores, max_area, out=None):
     return out
 
 
+# ------------------------------------------------------------------ prompts from ground truth (csrc/gtprompt.hip)
+GP_STATS = 9        # int64 per kept component of s2h_cc_components (csrc/gtprompt.h)
+GP_MAX_INDEX = 255  # kept components per image its uint8 index image can name
+GP_MAX_REACH = 32   # a morphology window reaches at most this far to either side
+GP_CHUNK = 4096     # pixels per counting block of s2h_mask_rank_select
+
+
+def cc_label_u8(mask, positive=True):
+    """cc_label on byte masks (s2h_cc_label_u8): mask [N, H, W] uint8 contiguous, foreground is != 0
+    (`positive`) or == 0.  -> (labels, areas) int32 [N, H, W] as cc_label"""
+    assert mask.dim() == 3 and mask.dtype == torch.uint8 and mask.is_contiguous()
+    _dev(mask)
+    N, H, W = mask.shape
+    labels = torch.empty(N, H, W, device=mask.device, dtype=torch.int32)
+    areas = torch.empty(N, H, W, device=mask.device, dtype=torch.int32)
+    call("s2h_cc_label_u8", N, H, W, ptr(mask), int(bool(positive)), ptr(labels), ptr(areas), stream())
+    return labels, areas
+
+
+def rle_runs(counts_list, H, W):
+    """COCO counts of A annotations of one H x W image -> (run_off int32 [A + 1], run_end int32 [sum of the
+    run counts]) host numpy, what s2h_rle_decode reads; every annotation's counts must be >= 0 and sum to H W"""
+    H, W = int(H), int(W)
+    run_off, ends = [0], []
+    for a, cnts in enumerate(counts_list):
+        c = np.asarray(cnts, dtype=np.int64).reshape(-1)
+        if c.size == 0 or (c < 0).any() or int(c.sum()) != H * W:
+            raise ValueError(f"annotation {a}: RLE counts cover {int(c.sum())} pixels in {c.size} runs, "
+                             f"the mask has {H * W}")
+        ends.append(np.cumsum(c))
+        run_off.append(run_off[-1] + c.size)
+    run_end = np.concatenate(ends) if ends else np.zeros(0, np.int64)
+    return np.asarray(run_off, np.int32), run_end.astype(np.int32)
+
+
+def rle_decode(counts_list, H, W, device="cuda"):
+    """COCO RLE counts (lists of run lengths, column-major, starting with zeros) of A annotations of one H x W
+    image -> uint8 [A, H, W] on the device (s2h_rle_decode); only the run boundaries are uploaded"""
+    run_off, run_end = rle_runs(counts_list, H, W)
+    A = run_off.size - 1
+    mask = torch.empty(A, int(H), int(W), device=device, dtype=torch.uint8)
+    _dev(mask)
+    if A == 0:
+        return mask
+    off_d = torch.from_numpy(run_off).to(mask.device)
+    end_d = torch.from_numpy(run_end).to(mask.device)
+    call("s2h_rle_decode", A, int(H), int(W), ptr(off_d), ptr(end_d), ptr(mask), stream())
+    return mask
+
+
+def morph_rect(mask, op, y_win, x_win, out=None):
+    """rectangular dilation (op "dilate" / 0) or erosion ("erode" / 1) of byte masks [N, H, W]
+    (s2h_morph_rect): out(y, x) = OR / AND of mask(y + dy, x + dx) over dy in [y_win[0], y_win[1]] and dx in
+    [x_win[0], x_win[1]] restricted to the image.  -32 <= lo <= 0 <= hi <= 32.  -> uint8 [N, H, W] of 0 / 1"""
+    op = {"dilate": 0, "erode": 1}.get(op, op)
+    assert op in (0, 1), "op is dilate (0) or erode (1)"
+    assert mask.dim() == 3 and mask.dtype == torch.uint8 and mask.is_contiguous()
+    (y_lo, y_hi), (x_lo, x_hi) = (int(v) for v in y_win), (int(v) for v in x_win)
+    for lo, hi in ((y_lo, y_hi), (x_lo, x_hi)):
+        if not (-GP_MAX_REACH <= lo <= 0 <= hi <= GP_MAX_REACH):
+            raise ValueError(f"window ({lo}, {hi}) is outside -{GP_MAX_REACH} <= lo <= 0 <= hi <= {GP_MAX_REACH}")
+    if out is None:
+        out = torch.empty_like(mask)
+    assert out.shape == mask.shape and out.dtype == torch.uint8 and out.is_contiguous()
+    assert out.data_ptr() != mask.data_ptr() or mask.numel() == 0, "morph_rect does not run in place"
+    _dev(mask, out)
+    N, H, W = mask.shape
+    work = torch.empty_like(mask)
+    call("s2h_morph_rect", N, H, W, ptr(mask), op, y_lo, y_hi, x_lo, x_hi, ptr(out), ptr(work), stream())
+    return out
+
+
+def cc_components(labels, areas, min_area, grid=None, capacity=None):
+    """the components of area >= min_area of images labelled by cc_label / cc_label_u8, per image in raster
+    order of their first pixel (s2h_cc_components).  grid: uint8 [H, W] on the device or None.
+    -> (hdr int32 [2 N + 2]: count and offset per image, total, status (1: an image has more than 255 kept
+    components and `index` is unusable); stats int64 [capacity, 9]: root label, area, xmin, ymin, xmax, ymax,
+    n_sel, sum x, sum y of the grid-selected pixels -- only the first min(total, capacity) rows are written;
+    index uint8 [N, H, W]: 0 or the 1-based number of the pixel's kept component within its image).
+    capacity None = 255 N, enough whenever the status is 0."""
+    assert labels.dim() == 3 and labels.dtype == torch.int32 and labels.is_contiguous()
+    assert areas.shape == labels.shape and areas.dtype == torch.int32 and areas.is_contiguous()
+    _dev(labels, areas)
+    N, H, W = labels.shape
+    if grid is not None:
+        assert grid.shape == (H, W) and grid.dtype == torch.uint8 and grid.is_contiguous()
+        _dev(grid)
+    capacity = GP_MAX_INDEX * N if capacity is None else int(capacity)
+    dev = labels.device
+    hdr = torch.empty(2 * N + 2, device=dev, dtype=torch.int32)
+    stats = torch.empty(max(capacity, 1), GP_STATS, device=dev, dtype=torch.int64)[:capacity]
+    index = torch.empty(N, H, W, device=dev, dtype=torch.uint8)
+    work = torch.empty(max(1, N * H * W + N * ((H * W + 255) // 256)), device=dev, dtype=torch.int32)
+    call("s2h_cc_components", N, H, W, ptr(labels), ptr(areas), int(min_area), ptr(grid), capacity, ptr(hdr),
+         ptr(stats), ptr(index), ptr(work), stream())
+    return hdr, stats, index
+
+
+def mask_rank_select(q_img, q_label, q_neg, q_rank, labels, grid=None):
+    """per query the q_rank-th pixel, row-major, of image q_img among those with (labels == q_label) != q_neg
+    that lie on the grid (s2h_mask_rank_select).  The four query arrays: int32 [Q] on the device.
+    -> (xy int32 [Q, 2] = (x, y), (-1, -1) when the rank is not below the count; count int32 [Q])"""
+    assert labels.dim() == 3 and labels.dtype == torch.int32 and labels.is_contiguous()
+    N, H, W = labels.shape
+    Q = q_img.numel()
+    for t in (q_img, q_label, q_neg, q_rank):
+        assert t.dim() == 1 and t.numel() == Q and t.dtype == torch.int32 and t.is_contiguous()
+    _dev(labels, q_img, q_label, q_neg, q_rank)
+    if grid is not None:
+        assert grid.shape == (H, W) and grid.dtype == torch.uint8 and grid.is_contiguous()
+        _dev(grid)
+    dev = labels.device
+    xy = torch.empty(Q, 2, device=dev, dtype=torch.int32)
+    count = torch.empty(Q, device=dev, dtype=torch.int32)
+    work = torch.empty(max(1, Q * ((H * W + GP_CHUNK - 1) // GP_CHUNK)), device=dev, dtype=torch.int32)
+    call("s2h_mask_rank_select", Q, ptr(q_img), ptr(q_label), ptr(q_neg), ptr(q_rank), N, H, W, ptr(labels),
+         ptr(grid), ptr(xy), ptr(count), ptr(work), stream())
+    return xy, count
+
+
 RLE_HDR = 8  # int32 per category of s2h_rle_transitions' header (csrc/rle_scan.h)
 
 
