@@ -536,6 +536,31 @@ int s2h_window_pad(int dt, int B, int H, int W, int C, int ws, const void* src, 
 /* Its bias gradient: out[c] += sum of win[row][c] over the padded rows of the windowed tensor
  * (fixed-order partial sums). */
 int s2h_window_pad_colsum(int dt, int B, int H, int W, int C, int ws, const void* win, float* out, hipStream_t st);
+/* The same over rows that are already compact: src [B * P][C] bf16 holds only the padded rows, in that
+ * enumeration order (per image the rows y >= H, then x >= W); same chunks and fixed-order finish, so
+ * every column's sum has the bits s2h_window_pad_colsum gives for the partitioned tensor. */
+int s2h_pad_rows_colsum(int B, int P, int C, const void* src, float* out, hipStream_t st);
+/* Padded-window attention straight from the image layout (Hiera's windows that need padding,
+ * hieradet.py:146; bf16, head dim hd 32..128, ws * ws in [128, 512]).  s2h_window_map builds the row
+ * map of a geometry on the host: n = s2h_window_map_len ints, [row: nW x L][padidx: nW x L][sets: nW]
+ * (L = ws * ws, nW windows per image; row = token index y * W + x or -1 for padding; padidx = the
+ * padded position's row in s2h_pad_rows_colsum's order or -1; sets = bit s set when positions
+ * 16 s .. 16 s + 15 hold a token), every entry range-checked.  The kernels take a device copy.
+ * s2h_flash_win_ok: 1 when the mode applies to (dt, batch, geometry) -- it needs enough batch-heads
+ * that the partitioned launches would not split their key range; 0 = partition and use s2h_attn_*.
+ * Forward: qkv [B, H, W, 3 d] (d = NH * hd), padrow [3 d] bf16 (the projection's bias, as
+ * s2h_window_pad rounds it) -> o [B, H, W, d], lse [B * nW * NH][L] (+inf at padded positions).
+ * Backward: dout [B, H, W, d], zrow >= hd zeros -> dqkv [B, H, W, 3 d] (every real token's dq | dk | dv),
+ * dpad [B * P][2 d] (dk | dv of the padded keys); di [B * nW * NH][L] scratch.  Results equal the
+ * partitioned path's bit for bit. */
+int64_t s2h_window_map_len(int H, int W, int ws);
+int s2h_window_map(int H, int W, int ws, int* out, int64_t n);
+int s2h_flash_win_ok(int dt, int B, int H, int W, int ws, int NH, int hd);
+int s2h_flash_win_fwd(int B, int H, int W, int ws, int NH, int hd, const void* qkv, const void* padrow, const int* map,
+                      void* o, float* lse, float scale, hipStream_t st);
+int s2h_flash_win_bwd(int B, int H, int W, int ws, int NH, int hd, const void* qkv, const void* padrow,
+                      const void* zrow, const int* map, const void* o, const void* dout, void* dqkv, void* dpad,
+                      const float* lse, float* di, float scale, hipStream_t st);
 /* FPN top-down: out = lat + nearest_up2(prev) (image_encoder.py:102-134). */
 int s2h_up2_add(int dt, int B, int H, int W, int C, const void* lat, const void* prev, void* out, hipStream_t st);
 /* Backward of the nearest 2x upsample: dprev (+)= 2x2 sum of dout. */

@@ -727,25 +727,30 @@ extern "C" int s2h_window_pad(int dt, int B, int H, int W, int C, int ws, const 
 // groups of 16 B x 8 row lanes over one chunk of padded rows; the 8 lanes' sums are added in fixed
 // order through LDS, the chunk's partial row goes to the workspace and det_colsum finishes (or float
 // atomics without the deterministic workspace).
-template <typename T>
+// COMPACT: `win` holds the padded rows only, [B * P][C] in this enumeration order (the padded-window
+// attention's padded-key gradients, s2h_pad_rows_colsum): same chunks, lanes and sums, no index math.
+template <typename T, bool COMPACT = false>
 __global__ __launch_bounds__(256) void window_pad_colsum_kernel(int B, int H, int W, int C, int ws, const T* win,
                                                                 int rows_per_chunk, float* out, float* part) {
   constexpr int VEC = V16<T>::VEC;
   const int cg = threadIdx.x & 31, lane = threadIdx.x >> 5;
   const int c = (blockIdx.x * 32 + cg) * VEC;
   const int nh = (H + ws - 1) / ws, nw = (W + ws - 1) / ws, Hp = nh * ws, Wp = nw * ws;
-  const int P = Hp * Wp - H * W, rows = B * P, top = (Hp - H) * Wp;
+  const int P = COMPACT ? H : Hp * Wp - H * W, rows = B * P, top = (Hp - H) * Wp;  // COMPACT: H carries P
   const int r0 = blockIdx.y * rows_per_chunk, r1 = min(rows, r0 + rows_per_chunk);
   float acc[VEC];
 #pragma unroll
   for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
   if (c < C) {
     for (int r = r0 + lane; r < r1; r += 8) {
-      const int b = r / P;
-      int q = r - b * P, y, x;
-      if (q < top) { y = H + q / Wp; x = q - (q / Wp) * Wp; }
-      else { q -= top; y = q / (Wp - W); x = W + q - y * (Wp - W); }
-      const int64_t wrow = (((int64_t)(b * nh + y / ws) * nw + x / ws) * ws + y % ws) * ws + x % ws;
+      int64_t wrow = r;
+      if constexpr (!COMPACT) {
+        const int b = r / P;
+        int q = r - b * P, y, x;
+        if (q < top) { y = H + q / Wp; x = q - (q / Wp) * Wp; }
+        else { q -= top; y = q / (Wp - W); x = W + q - y * (Wp - W); }
+        wrow = (((int64_t)(b * nh + y / ws) * nw + x / ws) * ws + y % ws) * ws + x % ws;
+      }
       float v[VEC];
       V16<T>::load(win + wrow * C + c, v);
 #pragma unroll
@@ -793,6 +798,28 @@ extern "C" int s2h_window_pad_colsum(int dt, int B, int H, int W, int C, int ws,
   else
     hipLaunchKernelGGL(window_pad_colsum_kernel<float>, grid, dim3(256), 0, st, B, H, W, C, ws, (const float*)win, rpc,
                        out, part);
+  if (part && !deferred) det_colsum(1, nchunk, C, part, out, 1, st);
+  return (int)hipGetLastError();
+}
+
+// out (fp32 [C]) += the column sums of src [B * P][C] (bf16): window_pad_colsum over rows that are
+// already compact and in its order -- the same chunking, lane order and fixed-order finish, so a
+// column's sum has the bits s2h_window_pad_colsum gives for the partitioned gradient.
+extern "C" int s2h_pad_rows_colsum(int B, int P, int C, const void* src, float* out, hipStream_t st) {
+  const int64_t rows = (int64_t)B * P;
+  if (C % 8 || !al16(src) || rows >= (1ll << 31)) return (int)hipErrorInvalidValue;
+  if (rows <= 0 || C <= 0) return 0;
+  int rpc = 32;
+  int nchunk = (int)((rows + rpc - 1) / rpc);
+  if (nchunk > 256) {
+    rpc = (int)((rows + 255) / 256);
+    nchunk = (int)((rows + rpc - 1) / rpc);
+  }
+  float* deferred = s2h_defer_sink(nchunk, C, out, 0, nullptr, st);
+  float* part = deferred ? deferred : s2h_det_ws(nchunk * C * (int64_t)sizeof(float));
+  const dim3 grid((unsigned)((C / 8 + 31) / 32), (unsigned)nchunk);
+  hipLaunchKernelGGL((window_pad_colsum_kernel<bf16, true>), grid, dim3(256), 0, st, B, P, 1, C, 1, (const bf16*)src, rpc,
+                     out, part);
   if (part && !deferred) det_colsum(1, nchunk, C, part, out, 1, st);
   return (int)hipGetLastError();
 }

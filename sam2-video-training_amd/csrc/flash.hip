@@ -25,6 +25,8 @@
 //     writes u' = [D M | rowsum(D) | 0 x 7] (72 columns); one [rows x 72] x [72 x 256] GEMM with
 //     [Wv | bv] finishes O.  P V costs a quarter of its MFMAs and V tiles a quarter of their bytes;
 //     the V projection of the whole bank (up to 7196 x 13 rows per frame and layer) disappears.
+#include <vector>
+
 #include "flash_common.h"
 
 int s2h_prof_begin(hipStream_t st, int kind, int64_t m0, int64_t m1, int64_t m2, int64_t m3, int64_t m4);
@@ -50,6 +52,7 @@ struct FlashArgs {
   float* ws_o;   // [splits][BH*Lq][DP] unnormalised partial O (splits > 1)
   float* ws_ml;  // [splits][BH*Lq][2] (m in log2 units, l)
   int prio;      // waves 4-7 at s_setprio 1 (A/B: s2h_flash_variant bit 3)
+  WinArgs win;   // padded-window mode (flash_fwd_kernel WIN; flash_common.h)
 };
 
 // dropout: none / counter hash / counter hash + keep bitmap store (template: no per-tile tests)
@@ -64,9 +67,14 @@ enum { FDROP_NONE = 0, FDROP_HASH = 1, FDROP_BITS = 2 };
 // kernel's LDS read traffic per query halves; the workgroup covers 128 QS query rows)
 // NSB: stages in the K / V ring -- 2: two barriers per tile; 3 (the V-fold default, flash_launch): tile
 // it + 1 in flight across tile it's compute, one barrier per tile (the backward's round-6 ring)
-template <int DP, int DROP, int DV = DP, int QS = 1, int NSB = 2>
+// WIN: padded-window mode (flash_common.h WinArgs): rows through the window's map, padded keys read the
+// bias row, padded queries are neither loaded nor stored (their LSE is +inf, so the backward's
+// recomputed P is exactly 0 for them) and a wave whose query rows are all padding skips the tile
+// arithmetic.  Every real query sees the same key tiles in the same order as on the partitioned copy.
+template <int DP, int DROP, int DV = DP, int QS = 1, int NSB = 2, bool WIN = false>
 __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_fwd_kernel(FlashArgs a) {
   static_assert(NSB == 2 || NSB == 3, "ring depth");
+  static_assert(!WIN || (DROP == FDROP_NONE && DV == DP && DP <= 128), "padded-window mode: plain, no dropout");
   constexpr bool FOLD = DV != DP;
   constexpr int QB = FL_QB * QS;
   const uint32_t hkey = DROP != FDROP_NONE ? s2h_hash_key(s2h_seed(a.seed, a.seed_off)) : 0u;
@@ -82,11 +90,22 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_fwd_kernel(FlashArgs a
   if (a.prio && w >= 4) __builtin_amdgcn_s_setprio(1);  // the second-dispatched half (MI355X_MICROARCH item 4)
   const WgIdx wi = wg_xcd_order();
   if (wi.y >= a.BH) return;  // grid padding
-  const int bh = wi.y, b = bh / a.H, h = bh % a.H;
+  const int bh = wi.y, h = bh % a.H;
+  const int b = WIN ? bh / a.H / a.win.nW : bh / a.H;  // WIN: the image (batch strides are per image)
   const int split = wi.z;
   int q[QS];  // this lane's query row in each set
 #pragma unroll
   for (int u = 0; u < QS; ++u) q[u] = wi.x * QB + (w * QS + u) * 16 + ql;
+  // WIN: the window's row map in LDS (Lq = Lk <= FL_WIN_MAXL positions)
+  __shared__ int wmap[WIN ? FL_WIN_MAXL : 1];
+  int qt[QS];  // WIN: token of the query row (-1: padding or past the window)
+  if constexpr (WIN) {
+    const int* gm = a.win.row + (int64_t)((bh / a.H) % a.win.nW) * a.Lq;
+    if (tid < a.Lq) wmap[tid] = gm[tid];
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < QS; ++u) qt[u] = q[u] < a.Lq ? wmap[q[u]] : -1;
+  }
   const bf16* Q = a.q + b * a.sqb + h * a.sqh;
   const bf16* K = a.k + b * a.skb + h * a.skh;
   const bf16* V = a.v + b * a.svb + h * a.svh;
@@ -95,9 +114,16 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_fwd_kernel(FlashArgs a
   const int t1 = min(ntiles_all, t0 + a.tiles_per_split);
   const int nt = t1 - t0;
 
+  const bf16* Kpad = WIN ? a.win.kpad + h * a.skh : nullptr;
+  const bf16* Vpad = WIN ? a.win.vpad + h * a.svh : nullptr;
   if (nt > 0) {
-    dma_tile_pad<DP, 64, FL_WAVES, true>(smem, K, a.skl, t0 * C::KT, a.Lk, w, lane, a.D);
-    dma_tile_pad<DV, 64, FL_WAVES, true>(smem + I::TILEB, V, a.svl, t0 * C::KT, a.Lk, w, lane, FOLD ? DV : a.D);
+    if constexpr (WIN) {
+      dma_tile_pad_win<DP>(smem, K, Kpad, wmap, a.skl, t0 * C::KT, a.Lk, w, lane, a.D);
+      dma_tile_pad_win<DV>(smem + I::TILEB, V, Vpad, wmap, a.svl, t0 * C::KT, a.Lk, w, lane, a.D);
+    } else {
+      dma_tile_pad<DP, 64, FL_WAVES, true>(smem, K, a.skl, t0 * C::KT, a.Lk, w, lane, a.D);
+      dma_tile_pad<DV, 64, FL_WAVES, true>(smem + I::TILEB, V, a.svl, t0 * C::KT, a.Lk, w, lane, FOLD ? DV : a.D);
+    }
   }
   const int npw = I::pieces(w), npv = IV::pieces(w);
   const int wu = __builtin_amdgcn_readfirstlane(w);
@@ -106,7 +132,10 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_fwd_kernel(FlashArgs a
   kdma.init(a.skl, w, lane, a.D);
   vdma.init(a.svl, w, lane, FOLD ? DV : a.D);
   auto issue = [&](char* Kn, int kk) {  // the K / V tile of keys kk.. into stage Kn
-    if (kk + C::KT <= a.Lk) {  // whole tile: precomputed offsets on an SGPR row base
+    if constexpr (WIN) {
+      dma_tile_pad_win<DP>(Kn, K, Kpad, wmap, a.skl, kk, a.Lk, w, lane, a.D);
+      dma_tile_pad_win<DV>(Kn + I::TILEB, V, Vpad, wmap, a.svl, kk, a.Lk, w, lane, a.D);
+    } else if (kk + C::KT <= a.Lk) {  // whole tile: precomputed offsets on an SGPR row base
       kdma.issue(Kn, K, a.skl, kk, wu);
       vdma.issue(Kn + I::TILEB, V, a.svl, kk, wu);
     } else {
@@ -122,11 +151,24 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_fwd_kernel(FlashArgs a
   for (int u = 0; u < QS; ++u)
 #pragma unroll
     for (int t = 0; t < C::NT; ++t) {
+      if constexpr (WIN) {
+        qf[u][t] = qt[u] >= 0 && 32 * t + 8 * g < a.D ? *(const bf16x8*)(Q + (int64_t)qt[u] * a.sql + 32 * t + 8 * g)
+                                                       : bf16x8{};
+        continue;
+      }
       if (q[u] < a.Lq && 32 * t + 8 * g < a.D)
         qf[u][t] = *(const bf16x8*)(Q + (int64_t)q[u] * a.sql + 32 * t + 8 * g);
       else
         qf[u][t] = bf16x8{};
     }
+  // WIN: does this wave hold a real query at all (wave-uniform)
+  bool wact = true;
+  if constexpr (WIN) {
+    bool any = false;
+#pragma unroll
+    for (int u = 0; u < QS; ++u) any |= qt[u] >= 0;
+    wact = __builtin_amdgcn_ballot_w64(any) != 0;
+  }
   // compiler-visible vmcnt(0): retires the Q loads in the compiler's own bookkeeping too;
   // otherwise it keeps them "maybe pending" around the key loop and waits vmcnt(0) before
   // the first MFMA of every tile -- which also drains the (asm, invisible) K/V prefetch
@@ -173,6 +215,7 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_fwd_kernel(FlashArgs a
     }
     cur = cur == NSB - 1 ? 0 : cur + 1;
 
+    if (!WIN || wact) {
     // ---- S^T = K Q^T: four 16-key blocks, key = 16*kb + 4g + r on the accumulator row
     f32x4 s[QS][4];
     __builtin_amdgcn_sched_barrier(0);
@@ -313,6 +356,7 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_fwd_kernel(FlashArgs a
     }
     sched_reads_ahead<2 * NDV, 4, 2, QS>();
     __builtin_amdgcn_sched_barrier(0);
+    }
     if constexpr (NSB == 2) {  // every wave done reading this stage before it is refilled (LDS reads retired first)
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
@@ -323,8 +367,14 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_fwd_kernel(FlashArgs a
 #pragma unroll
   for (int u = 0; u < QS; ++u) {
     if (q[u] >= a.Lq) continue;
+    if constexpr (WIN) {
+      if (qt[u] < 0) {  // padded query: no O; LSE = +inf makes the backward's P of this row exactly 0
+        if (g == 0) a.lse[(int64_t)bh * a.Lq + q[u]] = INFINITY;
+        continue;
+      }
+    }
     if (a.splits == 1) {
-      bf16* O = a.o + b * a.sob + h * a.soh + (int64_t)q[u] * a.sol;
+      bf16* O = a.o + b * a.sob + h * a.soh + (int64_t)(WIN ? qt[u] : q[u]) * a.sol;
       const float inv = l[u] > 0.f ? 1.f / l[u] : 0.f;
 #pragma unroll
       for (int d = 0; d < NDV; ++d) {
@@ -606,6 +656,124 @@ int s2h_flash_fwd(int B, int H, int Lq, int Lk, int D,
   if (D == 256) return flash_launch<256>(a, st);
   if (D > 64) return qs == 2 ? flash_launch<128, 128, 2>(a, st) : flash_launch<128>(a, st);  // 72..128
   return qs == 2 ? flash_launch<64, 64, 2>(a, st) : flash_launch<64>(a, st);                 // 32..64
+}
+
+// ---------------------------------------------------------------------------- padded windows
+// Row map of a geometry (H, W, ws), built on the host (flash_common.h WinArgs): n = 2 nW L + nW ints,
+// [row: nW x L][padidx: nW x L][sets: nW] with L = ws^2 and nW = ceil(H / ws) ceil(W / ws) windows per
+// image.  padidx enumerates the padded positions of an image as window_pad_colsum does: the rows
+// y >= H (all x of the padded width), then the rows y < H with x >= W.  Every entry is checked before
+// the table is handed out (a bad one would be an out-of-bounds row in the kernels).
+extern "C" int64_t s2h_window_map_len(int H, int W, int ws) {
+  if (H <= 0 || W <= 0 || ws <= 0) return 0;
+  const int64_t nW = (int64_t)((H + ws - 1) / ws) * ((W + ws - 1) / ws), L = (int64_t)ws * ws;
+  return 2 * nW * L + nW;
+}
+extern "C" int s2h_window_map(int H, int W, int ws, int* out, int64_t n) {
+  if (H <= 0 || W <= 0 || ws <= 0 || out == nullptr || n != s2h_window_map_len(H, W, ws)) return (int)hipErrorInvalidValue;
+  const int nh = (H + ws - 1) / ws, nw = (W + ws - 1) / ws, nW = nh * nw, L = ws * ws;
+  if (L > FL_WIN_MAXL || (int64_t)H * W >= (1ll << 31)) return (int)hipErrorInvalidValue;
+  const int Hp = nh * ws, Wp = nw * ws, P = Hp * Wp - H * W, top = (Hp - H) * Wp;
+  int* row = out;
+  int* pad = out + (int64_t)nW * L;
+  int* sets = out + 2 * (int64_t)nW * L;
+  for (int wn = 0; wn < nW; ++wn) {
+    uint32_t m = 0;
+    for (int l = 0; l < L; ++l) {
+      const int y = (wn / nw) * ws + l / ws, x = (wn % nw) * ws + l % ws;
+      const bool real = y < H && x < W;
+      row[wn * L + l] = real ? y * W + x : -1;
+      pad[wn * L + l] = real ? -1 : (y >= H ? (y - H) * Wp + x : top + y * (Wp - W) + (x - W));
+      if (real) m |= 1u << (l / 16);
+    }
+    sets[wn] = (int)m;
+  }
+  // validity: tokens within [0, H W) and each exactly once, padded rows within [0, P) and each exactly once
+  std::vector<char> seen_t((size_t)H * W, 0), seen_p((size_t)P, 0);
+  for (int64_t i = 0; i < (int64_t)nW * L; ++i) {
+    const int t = row[i], q = pad[i];
+    if ((t < 0) == (q < 0)) return (int)hipErrorInvalidValue;
+    if (t >= 0) {
+      if (t >= H * W || seen_t[t]++) return (int)hipErrorInvalidValue;
+    } else {
+      if (t != -1 || q >= P || seen_p[q]++) return (int)hipErrorInvalidValue;
+    }
+  }
+  for (char c : seen_t) if (!c) return (int)hipErrorInvalidValue;
+  for (char c : seen_p) if (!c) return (int)hipErrorInvalidValue;
+  return 0;
+}
+
+// The mode applies to: bf16, a flash-eligible window (>= 128 positions, head dim 32..128 in steps of
+// 8), <= FL_WIN_MAXL positions, 16-B aligned rows, per-image extents within the 32-bit DMA offsets, and
+// enough batch-heads that the partitioned launches would not split their key range (flash_plan,
+// flash_bwd_plan: a split sums fp32 partials in another order, and the mode must give the same bits; the
+// key-split forms of the mode are not built).
+int s2h_flash_bwd_dq_splits(int BH, int Lq, int Lk);
+extern "C" int s2h_flash_win_ok(int dt, int B, int H, int W, int ws, int NH, int hd) {
+  if (B <= 0 || H <= 0 || W <= 0 || ws <= 0 || NH <= 0 || hd <= 0) return 0;
+  const int64_t L = (int64_t)ws * ws, d = (int64_t)NH * hd;
+  if (L > FL_WIN_MAXL || hd > 128 || !s2h_flash_eligible(dt, (int)L, hd)) return 0;
+  if ((int64_t)H * W * 3 * d >= (1ll << 31)) return 0;
+  const int64_t bh = (int64_t)B * ((H + ws - 1) / ws) * ((W + ws - 1) / ws) * NH;
+  if (bh >= (1ll << 24)) return 0;
+  int splits, tps;
+  flash_plan((int)bh, (int)L, (int)L, splits, tps, flash_qs(false, hd));
+  if (splits != 1 || s2h_flash_bwd_dq_splits((int)bh, (int)L, (int)L) != 1) return 0;
+  return 1;
+}
+
+// fills the WinArgs of a launch from the device map (s2h_window_map's layout)
+void s2h_win_args(WinArgs& wa, const int* map, int H, int W, int ws) {
+  const int nh = (H + ws - 1) / ws, nw = (W + ws - 1) / ws, nW = nh * nw, L = ws * ws;
+  wa.row = map;
+  wa.padidx = map + (int64_t)nW * L;
+  wa.sets = (const uint32_t*)(map + 2 * (int64_t)nW * L);
+  wa.nW = nW;
+  wa.P = nh * ws * nw * ws - H * W;
+}
+
+// Forward of the padded-window attention: qkv [B, H, W, 3 d] (d = NH hd; q, k, v thirds, heads
+// adjacent), padrow [3 d] bf16 (the projection's bias as window_pad writes it), map (device copy of
+// s2h_window_map) -> o [B, H, W, d], lse [B nW NH][L] (+inf at padded positions).
+extern "C" int s2h_flash_win_fwd(int B, int H, int W, int ws, int NH, int hd, const void* qkv, const void* padrow,
+                                 const int* map, void* o, float* lse, float scale, hipStream_t st) {
+  if (B <= 0) return 0;
+  if (!s2h_flash_win_ok(S2H_BF16, B, H, W, ws, NH, hd) || !qkv || !padrow || !map || !o || !lse) return (int)hipErrorInvalidValue;
+  if ((((uintptr_t)qkv | (uintptr_t)padrow | (uintptr_t)o) & 15) != 0) return (int)hipErrorInvalidValue;
+  const int64_t d = (int64_t)NH * hd;
+  const int L = ws * ws;
+  FlashArgs a = {};
+  s2h_win_args(a.win, map, H, W, ws);
+  a.D = hd;
+  a.BH = B * a.win.nW * NH; a.H = NH; a.Lq = L; a.Lk = L;
+  const bf16* x = (const bf16*)qkv;
+  const bf16* pr = (const bf16*)padrow;
+  a.q = x; a.sqb = (int64_t)H * W * 3 * d; a.sqh = hd; a.sql = 3 * d;
+  a.k = x + d; a.skb = a.sqb; a.skh = hd; a.skl = 3 * d;
+  a.v = x + 2 * d; a.svb = a.sqb; a.svh = hd; a.svl = 3 * d;
+  a.win.qpad = pr; a.win.kpad = pr + d; a.win.vpad = pr + 2 * d;
+  a.o = (bf16*)o; a.sob = (int64_t)H * W * d; a.soh = hd; a.sol = d;
+  a.lse = lse;
+  a.sl2 = scale * FL_LOG2E;
+  a.inv_keep = 1.f;
+  a.seed_off = s2h_rng_offset_ptr();
+  a.splits = 1;
+  a.tiles_per_split = (L + 63) / 64;
+  a.prio = (s2h_flash_variant() >> 3) & 1;
+  const int qs = flash_qs(false, hd);
+  const dim3 grid((L + FL_QB * qs - 1) / (FL_QB * qs), pad_bh8(a.BH), 1);
+  // the profiler record keeps the partitioned launch's logical shape
+  const int slot = s2h_prof_begin(st, 1, (int64_t)a.BH, L, L, hd, 2);
+  if (hd > 64) {
+    if (qs == 2) hipLaunchKernelGGL((flash_fwd_kernel<128, FDROP_NONE, 128, 2, 2, true>), grid, dim3(FL_WAVES * 64), 0, st, a);
+    else hipLaunchKernelGGL((flash_fwd_kernel<128, FDROP_NONE, 128, 1, 2, true>), grid, dim3(FL_WAVES * 64), 0, st, a);
+  } else {
+    if (qs == 2) hipLaunchKernelGGL((flash_fwd_kernel<64, FDROP_NONE, 64, 2, 2, true>), grid, dim3(FL_WAVES * 64), 0, st, a);
+    else hipLaunchKernelGGL((flash_fwd_kernel<64, FDROP_NONE, 64, 1, 2, true>), grid, dim3(FL_WAVES * 64), 0, st, a);
+  }
+  s2h_prof_end(slot, st);
+  return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------- V-fold

@@ -68,6 +68,7 @@ struct FlashBwdArgs {
   int fr_nrot[S2H_MAX_FRAMES];
   int fr_nrotq[S2H_MAX_FRAMES];
   int prio;  // bit 0: dK kernel, bit 1: dQ kernel -- waves 4-7 at s_setprio 1 (A/B: s2h_flash_variant bits 1-2)
+  WinArgs win;  // padded-window mode (the WIN kernels; flash_common.h)
 };
 
 // The frame table is read straight from the kernarg segment (scalar loads): indexing the by-value
@@ -146,9 +147,13 @@ enum { DROP_NONE = 0, DROP_BITS = 1, DROP_HASH = 2 };
 // ------------------------------------------------------------------ dQ
 // NSB: stages in the K / V ring (2, or 3: a tile in flight across the next one's compute, one barrier
 // per tile); PF: LDS fragment reads kept ahead of their MFMAs in the S / dP phase.
-template <int DP, int DROP, int DV = DP, int NSB = 2, int PF = 4>
+// WIN: padded-window mode (flash_common.h WinArgs; single-frame launches, no key split): Q / O / dO /
+// dQ rows through the window's map, padded keys read the bias row; a padded query stores Di = 0 (its
+// dO is zero) and nothing else, and a wave whose queries are all padding skips the tile arithmetic.
+template <int DP, int DROP, int DV = DP, int NSB = 2, int PF = 4, bool WIN = false>
 __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dq_kernel(FlashBwdArgs a) {
   static_assert(NSB == 2 || NSB == 3, "ring depth");
+  static_assert(!WIN || (DROP == DROP_NONE && DV == DP && DP <= 128), "padded-window mode: plain, no dropout");
   constexpr bool FOLD = DV != DP;
   const uint64_t seed = DROP == DROP_HASH ? s2h_seed(a.seed, a.seed_off) : 0;
   using C = FlashCfg<DP, 64>;
@@ -162,15 +167,39 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dq_kernel(FlashBwd
   if ((a.prio & 2) && w >= 4) __builtin_amdgcn_s_setprio(1);
   const WgIdx wi = wg_xcd_order();
   if (wi.y >= a.BH) return;  // grid padding
-  const int bh = wi.y, b = bh / a.H, h = bh % a.H;
+  const int bh = wi.y, h = bh % a.H;
+  const int b = WIN ? bh / a.H / a.win.nW : bh / a.H;  // WIN: the image (batch strides are per image)
   const int split = wi.z;
   const int q = wi.x * FL_QB + w * 16 + ql;
+  // WIN: the window's row map in LDS; qt = the query's token (-1: padding or past the window)
+  __shared__ int wmap[WIN ? FL_WIN_MAXL : 1];
+  int qt = -1;
+  if constexpr (WIN) {
+    const int* gm = a.win.row + (int64_t)((bh / a.H) % a.win.nW) * a.Lq;
+    if (tid < a.Lq) wmap[tid] = gm[tid];
+    __syncthreads();
+    qt = q < a.Lq ? wmap[q] : -1;
+  }
   const bf16* Q = a.q + b * a.sqb + h * a.sqh;
   const bf16* G = a.g + b * a.sgb + h * a.sgh;
-  const KvFrame fr = kv_frame(a, bh);
+  const KvFrame fr = WIN ? KvFrame{a.k + b * a.skb + h * a.skh, a.v + b * a.svb + h * a.svh, nullptr, nullptr, a.Lk, 0,
+                                   nullptr, 0}
+                         : kv_frame(a, bh);
   const bf16* K = fr.k;
   const bf16* V = fr.v;
   const int Lk = fr.Lk;
+  const bf16* Kpad = WIN ? a.win.kpad + h * a.skh : nullptr;
+  const bf16* Vpad = WIN ? a.win.vpad + h * a.svh : nullptr;
+  // the K / V tile of keys kk.. into stage image Kn
+  auto load_kv = [&](char* Kn, int kk) {
+    if constexpr (WIN) {
+      dma_tile_pad_win<DP>(Kn, K, Kpad, wmap, a.skl, kk, Lk, w, lane, a.D);
+      dma_tile_pad_win<DV>(Kn + I::TILEB, V, Vpad, wmap, a.svl, kk, Lk, w, lane, a.D);
+    } else {
+      dma_tile_pad<DP, 64, FL_WAVES, true>(Kn, K, a.skl, kk, Lk, w, lane, a.D);
+      dma_tile_pad<DV, 64, FL_WAVES, true>(Kn + I::TILEB, V, a.svl, kk, Lk, w, lane, FOLD ? DV : a.D);
+    }
+  };
   const int ntiles_all = (Lk + C::KT - 1) / C::KT;
   const int t0 = split * a.tiles_per_split;
   const int nt = min(ntiles_all, t0 + a.tiles_per_split) - t0;
@@ -184,29 +213,28 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dq_kernel(FlashBwd
   auto dma_bits = [&](int stage, int k0) { lds_dma4(KEEPQ + (k0 >> 5) + (lane & 1), bits_lds + stage * FL_WAVES * 256); };
 
   if (nt > 0) {
-    dma_tile_pad<DP, 64, FL_WAVES, true>(smem, K, a.skl, t0 * C::KT, Lk, w, lane, a.D);
-    dma_tile_pad<DV, 64, FL_WAVES, true>(smem + I::TILEB, V, a.svl, t0 * C::KT, Lk, w, lane, FOLD ? DV : a.D);
+    load_kv(smem, t0 * C::KT);
     if constexpr (bits) dma_bits(0, t0 * C::KT);
   }
   if (NSB == 3 && nt > 1) {
-    dma_tile_pad<DP, 64, FL_WAVES, true>(smem + STG, K, a.skl, (t0 + 1) * C::KT, Lk, w, lane, a.D);
-    dma_tile_pad<DV, 64, FL_WAVES, true>(smem + STG + I::TILEB, V, a.svl, (t0 + 1) * C::KT, Lk, w, lane, FOLD ? DV : a.D);
+    load_kv(smem + STG, (t0 + 1) * C::KT);
     if constexpr (bits) dma_bits(1, (t0 + 1) * C::KT);
   }
-  const bool qv = q < a.Lq;
+  const bool qv = WIN ? qt >= 0 : q < a.Lq;
+  const int qrow = WIN ? qt : q;  // the row of Q / O / dO / dQ
   bf16x8 qf[C::NT], gf[NTV];
 #pragma unroll
   for (int t = 0; t < C::NT; ++t) {
     const bool ok = qv && 32 * t + 8 * g < a.D;  // zero past the head dim
-    qf[t] = ok ? *(const bf16x8*)(Q + (int64_t)q * a.sql + 32 * t + 8 * g) : bf16x8{};
+    qf[t] = ok ? *(const bf16x8*)(Q + (int64_t)qrow * a.sql + 32 * t + 8 * g) : bf16x8{};
   }
 #pragma unroll
   for (int t = 0; t < NTV; ++t) {
     const bool ok = qv && (FOLD || 32 * t + 8 * g < a.D);
-    gf[t] = ok ? *(const bf16x8*)(G + (int64_t)q * a.sgl + 32 * t + 8 * g) : bf16x8{};
+    gf[t] = ok ? *(const bf16x8*)(G + (int64_t)qrow * a.sgl + 32 * t + 8 * g) : bf16x8{};
   }
   // V-fold: dr = du'[q, DV] (dO . bv), constant over the keys of the row
-  const float dr = FOLD && qv ? (float)G[(int64_t)q * a.sgl + DV] : 0.f;
+  const float dr = FOLD && qv ? (float)G[(int64_t)qrow * a.sgl + DV] : 0.f;
   const float lse2 = qv ? a.lse[(int64_t)bh * a.Lq + q] * FL_LOG2E : 0.f;
   // Di = rowsum(dO * O) of this lane's query from the dO fragments already in registers and the
   // matching O fragments, reduced over the 4 lanes (g) of the query: replaces a separate
@@ -217,7 +245,7 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dq_kernel(FlashBwd
 #pragma unroll
     for (int t = 0; t < NTV; ++t) {
       if (qv && (FOLD || 32 * t + 8 * g < a.D)) {
-        const bf16x8 of = *(const bf16x8*)(O + (int64_t)q * a.sol + 32 * t + 8 * g);
+        const bf16x8 of = *(const bf16x8*)(O + (int64_t)qrow * a.sol + 32 * t + 8 * g);
 #pragma unroll
         for (int j = 0; j < 8; ++j) di += (float)gf[t][j] * (float)of[j];
       }
@@ -225,13 +253,14 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dq_kernel(FlashBwd
     di += __shfl_xor(di, 16, 64);
     di += __shfl_xor(di, 32, 64);
     if constexpr (FOLD) {  // + dr * rowsum(D)
-      if (qv) di += dr * (float)O[(int64_t)q * a.sol + DV];
+      if (qv) di += dr * (float)O[(int64_t)qrow * a.sol + DV];
     }
   }
   // compiler-visible vmcnt(0): the compiler's own bookkeeping retires these loads here instead
   // of waiting vmcnt(0) inside the key loop (which would also drain the asm K/V prefetch)
   __builtin_amdgcn_s_waitcnt(0xF70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
-  if (split == 0 && g == 0 && qv) a.di[(int64_t)bh * a.Lq + q] = di;
+  if (split == 0 && g == 0 && (WIN ? q < a.Lq : qv)) a.di[(int64_t)bh * a.Lq + q] = di;  // WIN: 0 at padding
+  const bool wact = !WIN || __builtin_amdgcn_ballot_w64(qv) != 0;  // this wave holds a real query
   f32x4 acc[C::ND];  // dQ^T: row d = 16*db + 4g + r, column q
 #pragma unroll
   for (int d = 0; d < C::ND; ++d) acc[d] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -249,9 +278,7 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dq_kernel(FlashBwd
       else wait_kv_pieces<I::PPW_LO, IV::PPW_LO>(npw, npv);
     };
     auto issue = [&](int stage, int kk) {
-      char* Kn = smem + stage * STG;
-      dma_tile_pad<DP, 64, FL_WAVES, true>(Kn, K, a.skl, kk, Lk, w, lane, a.D);
-      dma_tile_pad<DV, 64, FL_WAVES, true>(Kn + I::TILEB, V, a.svl, kk, Lk, w, lane, FOLD ? DV : a.D);
+      load_kv(smem + stage * STG, kk);
       if constexpr (bits) dma_bits(stage, kk);
     };
     if constexpr (NSB == 2) {
@@ -272,6 +299,7 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dq_kernel(FlashBwd
     }
     cur = cur == NSB - 1 ? 0 : cur + 1;
 
+    if (wact) {
     f32x4 s[4], dp[4];
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -347,6 +375,7 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dq_kernel(FlashBwd
       for (int d = 0; d < C::ND; ++d) acc[d] = mfma16(tr_frag_pad<I::ROWB>(Kb, 32 * c, 16 * d, lane), dsb[c], acc[d]);
     sched_reads_ahead<2 * C::ND, 4, 2>();
     __builtin_amdgcn_sched_barrier(0);
+    }
 
     if constexpr (NSB == 2) {  // every wave's reads of this stage retired before it is refilled
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -356,9 +385,9 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dq_kernel(FlashBwd
 
   if (!qv) return;
   if (a.splits == 1) {
-    bf16* DQ = a.dq + b * a.sdqb + h * a.sdqh + (int64_t)q * a.sdql;
+    bf16* DQ = a.dq + b * a.sdqb + h * a.sdqh + (int64_t)qrow * a.sdql;
     // inverse RoPE of the query gradient (frame-table launches, rope_q)
-    const int nrq = a.rope_q ? (a.nfr > 0 ? kargs()->fr_nrotq[b / a.bpf] : a.Lq) : 0;
+    const int nrq = !WIN && a.rope_q ? (a.nfr > 0 ? kargs()->fr_nrotq[b / a.bpf] : a.Lq) : 0;
     const float* rc = rope_row(a, q, nrq, a.rope_cos);
     const float* rsn = rope_row(a, q, nrq, a.rope_sin);
     RopeCS tab[C::ND];
@@ -408,8 +437,15 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_combine_kernel(FlashBwdArgs 
 // 8 waves x 16 keys, K / V
 // fragments in registers; Q / dO tiles of QT queries (64 for the 64 image: a 32-row tile would be
 // half a DMA piece per wave) consumed in 32-query halves.
-template <int DP, int DROP>
+// WIN: padded-window mode (flash_common.h WinArgs; single-frame launches): Q / dO tiles and the K / V
+// fragments through the window's map -- a padded query row is (bias row, zero dO, LSE = +inf so P = 0,
+// Di = 0), a padded key the bias row; dk / dv of a real key go to its token's row, of a padded key to the
+// compact buffer.  Query tiles without a real row are skipped (their dO, hence every term they add,
+// is exactly zero); a partly padded tile keeps its rows in place, so each key's accumulation groups
+// the same terms as on the partitioned copy.
+template <int DP, int DROP, bool WIN = false>
 __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dkv_kernel(FlashBwdArgs a) {
+  static_assert(!WIN || DROP == DROP_NONE, "padded-window mode: no dropout");
   const uint64_t seed = DROP == DROP_HASH ? s2h_seed(a.seed, a.seed_off) : 0;
   constexpr int QT = DP == 64 ? 64 : 32;
   using C = FlashCfg<DP, QT>;
@@ -417,9 +453,12 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dkv_kernel(FlashBw
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, kl = lane & 15;
   const WgIdx wi = wg_xcd_order();
   if (wi.y >= a.BH) return;  // grid padding
-  const int bh = wi.y, b = bh / a.H, h = bh % a.H;
+  const int bh = wi.y, h = bh % a.H;
+  const int b = WIN ? bh / a.H / a.win.nW : bh / a.H;  // WIN: the image (batch strides are per image)
   const int key = wi.x * FL_QB + w * 16 + kl;  // this lane's key (B-operand column)
-  const KvFrame fr = kv_frame(a, bh);
+  const KvFrame fr = WIN ? KvFrame{a.k + b * a.skb + h * a.skh, a.v + b * a.svb + h * a.svh,
+                                   a.dk + b * a.sdkb + h * a.sdkh, a.dv + b * a.sdvb + h * a.sdvh, a.Lk, 0, nullptr, 0}
+                         : kv_frame(a, bh);
   if (wi.x * FL_QB >= fr.Lk) return;  // frame-table launch: past this frame's keys
   const bool kv = key < fr.Lk;
   const bf16* Q = a.q + b * a.sqb + h * a.sqh;
@@ -427,15 +466,46 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dkv_kernel(FlashBw
   const bf16* K = fr.k;
   const bf16* V = fr.v;
   const int nt = (a.Lq + QT - 1) / QT;
-
-  dma_tile<DP, QT, FL_WAVES, true>(smem, Q, a.sql, 0, a.Lq, w, lane, a.D);
-  dma_tile<DP, QT, FL_WAVES, true>(smem + C::TILEB, G, a.sgl, 0, a.Lq, w, lane, a.D);
+  // WIN: the window's row map in LDS and the mask of its query tiles that hold a real row
+  __shared__ int wmap[WIN ? FL_WIN_MAXL : 1];
+  const int wn = WIN ? (bh / a.H) % a.win.nW : 0;
+  uint32_t tmask = 0xFFFFFFFFu;  // bit it: query tile it is processed
+  if constexpr (WIN) {
+    const int* gm = a.win.row + (int64_t)wn * a.Lq;
+    if (tid < a.Lq) wmap[tid] = gm[tid];
+    __syncthreads();
+    const uint32_t sets = __builtin_amdgcn_readfirstlane(a.win.sets[wn]);
+    tmask = 0u;
+    for (int it = 0; it < nt; ++it)
+      if ((sets >> (it * (QT / 16))) & ((1u << (QT / 16)) - 1u)) tmask |= 1u << it;
+  }
+  // the first / next processed tile at or after `it` (nt: none)
+  auto next_tile = [&](int it) {
+    if constexpr (WIN) {
+      while (it < nt && !((tmask >> it) & 1u)) ++it;
+    }
+    return it;
+  };
+  auto load_qg = [&](char* Qn, int qq0) {  // the Q / dO tile of queries qq0.. into stage image Qn
+    if constexpr (WIN) {
+      dma_tile_win<DP, QT>(Qn, Q, a.win.qpad + h * a.sqh, wmap, a.sql, qq0, a.Lq, w, lane, a.D);
+      dma_tile_win<DP, QT>(Qn + C::TILEB, G, a.win.zrow, wmap, a.sgl, qq0, a.Lq, w, lane, a.D);
+    } else {
+      dma_tile<DP, QT, FL_WAVES, true>(Qn, Q, a.sql, qq0, a.Lq, w, lane, a.D);
+      dma_tile<DP, QT, FL_WAVES, true>(Qn + C::TILEB, G, a.sgl, qq0, a.Lq, w, lane, a.D);
+    }
+  };
+  const int it0 = next_tile(0);
+  if (it0 < nt) load_qg(smem, it0 * QT);
+  const int kt = WIN && kv ? wmap[key] : -1;  // WIN: the key's token (-1: padding)
+  const bf16* Krow = WIN ? (kt >= 0 ? K + (int64_t)kt * a.skl : a.win.kpad + h * a.skh) : K + (int64_t)key * a.skl;
+  const bf16* Vrow = WIN ? (kt >= 0 ? V + (int64_t)kt * a.svl : a.win.vpad + h * a.svh) : V + (int64_t)key * a.svl;
   bf16x8 kf[C::NT], vf[C::NT];  // B operands: K^T / V^T [k = d][n = key]; zero past the head dim
 #pragma unroll
   for (int t = 0; t < C::NT; ++t) {
     const bool ok = kv && 32 * t + 8 * g < a.D;
-    kf[t] = ok ? *(const bf16x8*)(K + (int64_t)key * a.skl + 32 * t + 8 * g) : bf16x8{};
-    vf[t] = ok ? *(const bf16x8*)(V + (int64_t)key * a.svl + 32 * t + 8 * g) : bf16x8{};
+    kf[t] = ok ? *(const bf16x8*)(Krow + 32 * t + 8 * g) : bf16x8{};
+    vf[t] = ok ? *(const bf16x8*)(Vrow + 32 * t + 8 * g) : bf16x8{};
   }
   // compiler-visible vmcnt(0) for the fragment loads (see the dQ kernel)
   __builtin_amdgcn_s_waitcnt(0xF70);
@@ -448,10 +518,12 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dkv_kernel(FlashBw
   const float* LSE = a.lse + (int64_t)bh * a.Lq;
   const float* DI = a.di + (int64_t)bh * a.Lq;
 
-  for (int it = 0; it < nt; ++it) {
+  int stage = 0;
+  for (int it = it0; it < nt;) {
     const int q0 = it * QT;
-    char* Qb = smem + (it & 1) * 2 * C::TILEB;
+    char* Qb = smem + stage * 2 * C::TILEB;
     char* Gb = Qb + C::TILEB;
+    const int itn = next_tile(it + 1);
     // this tile's queries of this lane: q0 + 32*hf + 16*qb + 4g + r  (hf < QT/32; qb = 0, 1; r = 0..3)
     float4 lse4[QT / 16], di4[QT / 16];
 #pragma unroll
@@ -471,10 +543,8 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dkv_kernel(FlashBw
         di4[qb] = float4{dt[0], dt[1], dt[2], dt[3]};
       }
     }
-    if (it + 1 < nt) {
-      char* Qn = smem + ((it + 1) & 1) * 2 * C::TILEB;
-      dma_tile<DP, QT, FL_WAVES, true>(Qn, Q, a.sql, q0 + QT, a.Lq, w, lane, a.D);
-      dma_tile<DP, QT, FL_WAVES, true>(Qn + C::TILEB, G, a.sgl, q0 + QT, a.Lq, w, lane, a.D);
+    if (itn < nt) {
+      load_qg(smem + (stage ^ 1) * 2 * C::TILEB, itn * QT);
       wait_vmcnt<2 * C::PPW>();
     } else {
       wait_vmcnt<0>();
@@ -533,11 +603,23 @@ __global__ __launch_bounds__(FL_WAVES * 64, 1) void flash_bwd_dkv_kernel(FlashBw
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     wg_barrier();
+    stage ^= 1;
+    it = itn;
   }
 
   if (!kv) return;
   bf16* DK = fr.dk + (int64_t)key * a.sdkl;
   bf16* DV = fr.dv + (int64_t)key * a.sdvl;
+  if constexpr (WIN) {
+    if (kt >= 0) {
+      DK = fr.dk + (int64_t)kt * a.sdkl;
+      DV = fr.dv + (int64_t)kt * a.sdvl;
+    } else {  // padded key: its row of the compact buffer (heads adjacent, as in the image rows)
+      const int64_t prow = (int64_t)b * a.win.P + a.win.padidx[(int64_t)wn * a.Lq + key];
+      DK = a.win.dkpad + prow * a.win.sdpad + h * a.sdkh;
+      DV = a.win.dvpad + prow * a.win.sdpad + h * a.sdvh;
+    }
+  }
 #pragma unroll
   for (int d = 0; d < C::ND; ++d) {
     if (16 * d + 4 * g >= a.D) continue;
@@ -1223,6 +1305,70 @@ int s2h_flash_bwd(int B, int H, int Lq, int Lk, int D,
   if (D == 256) return flash_bwd_launch<256>(a, st);
   if (D > 64) return flash_bwd_launch<128>(a, st);  // 72..128: padded 128 image
   return flash_bwd_launch<64>(a, st);               // 32..64: padded 64 image
+}
+
+// Backward of the padded-window attention (flash.hip s2h_flash_win_fwd; the same qkv / padrow / map):
+// o, dout [B, H, W, d]; dqkv [B, H, W, 3 d] receives dq | dk | dv of every real token; dpad
+// [B * P][2 d] receives dk | dv of every padded key (P padded positions per image, in
+// window_pad_colsum's order); zrow: >= hd zero bf16; di [B nW NH][L] scratch.
+extern "C" int s2h_flash_win_ok(int dt, int B, int H, int W, int ws, int NH, int hd);
+int s2h_flash_bwd_dq_splits(int BH, int Lq, int Lk) {
+  int splits, tps;
+  flash_bwd_plan(BH, Lq, Lk, splits, tps);
+  return splits;
+}
+void s2h_win_args(WinArgs& wa, const int* map, int H, int W, int ws);
+extern "C" int s2h_flash_win_bwd(int B, int H, int W, int ws, int NH, int hd, const void* qkv, const void* padrow,
+                                 const void* zrow, const int* map, const void* o, const void* dout, void* dqkv,
+                                 void* dpad, const float* lse, float* di, float scale, hipStream_t st) {
+  if (B <= 0) return 0;
+  if (!s2h_flash_win_ok(S2H_BF16, B, H, W, ws, NH, hd) || !qkv || !padrow || !zrow || !map || !o || !dout || !dqkv ||
+      !dpad || !lse || !di)
+    return (int)hipErrorInvalidValue;
+  if ((((uintptr_t)qkv | (uintptr_t)padrow | (uintptr_t)zrow | (uintptr_t)o | (uintptr_t)dout | (uintptr_t)dqkv |
+        (uintptr_t)dpad) & 15) != 0)
+    return (int)hipErrorInvalidValue;
+  const int64_t d = (int64_t)NH * hd;
+  const int L = ws * ws;
+  FlashBwdArgs a = {};
+  s2h_win_args(a.win, map, H, W, ws);
+  a.D = hd;
+  a.BH = B * a.win.nW * NH; a.H = NH; a.Lq = L; a.Lk = L;
+  const bf16* x = (const bf16*)qkv;
+  const bf16* pr = (const bf16*)padrow;
+  bf16* dx = (bf16*)dqkv;
+  const int64_t sb3 = (int64_t)H * W * 3 * d, sb1 = (int64_t)H * W * d;
+  a.q = x; a.sqb = sb3; a.sqh = hd; a.sql = 3 * d;
+  a.k = x + d; a.skb = sb3; a.skh = hd; a.skl = 3 * d;
+  a.v = x + 2 * d; a.svb = sb3; a.svh = hd; a.svl = 3 * d;
+  a.o = (const bf16*)o; a.sob = sb1; a.soh = hd; a.sol = d;
+  a.g = (const bf16*)dout; a.sgb = sb1; a.sgh = hd; a.sgl = d;
+  a.dq = dx; a.sdqb = sb3; a.sdqh = hd; a.sdql = 3 * d;
+  a.dk = dx + d; a.sdkb = sb3; a.sdkh = hd; a.sdkl = 3 * d;
+  a.dv = dx + 2 * d; a.sdvb = sb3; a.sdvh = hd; a.sdvl = 3 * d;
+  a.win.qpad = pr; a.win.kpad = pr + d; a.win.vpad = pr + 2 * d;
+  a.win.zrow = (const bf16*)zrow;
+  a.win.dkpad = (bf16*)dpad; a.win.dvpad = (bf16*)dpad + d; a.win.sdpad = 2 * d;
+  a.lse = lse; a.di = di;
+  a.scale = scale; a.sl2 = scale * FL_LOG2E;
+  a.inv_keep = 1.f;
+  a.seed_off = s2h_rng_offset_ptr();
+  a.kw = 2 * ((L + 63) / 64);
+  a.splits = 1; a.tiles_per_split = (L + 63) / 64;
+  a.kv_splits = 1; a.kv_tiles_per_split = (L + 31) / 32;
+  a.prio = (s2h_flash_variant() >> 1) & 3;
+  const dim3 gq((L + FL_QB - 1) / FL_QB, pad_bh8(a.BH), 1), gk((L + FL_QB - 1) / FL_QB, pad_bh8(a.BH));
+  // the profiler record keeps the partitioned launch's logical shape
+  const int slot = s2h_prof_begin(st, 2, (int64_t)a.BH, L, L, hd, 2);
+  if (hd > 64) {
+    hipLaunchKernelGGL((flash_bwd_dq_kernel<128, DROP_NONE, 128, 2, 4, true>), gq, dim3(FL_WAVES * 64), 0, st, a);
+    hipLaunchKernelGGL((flash_bwd_dkv_kernel<128, DROP_NONE, true>), gk, dim3(FL_WAVES * 64), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((flash_bwd_dq_kernel<64, DROP_NONE, 64, 2, 4, true>), gq, dim3(FL_WAVES * 64), 0, st, a);
+    hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, DROP_NONE, true>), gk, dim3(FL_WAVES * 64), 0, st, a);
+  }
+  s2h_prof_end(slot, st);
+  return (int)hipGetLastError();
 }
 
 // eligible: the flash forward's domain (bf16, head_dim 256 or 32..128 padded to 64 / 128, >= 128

@@ -197,6 +197,59 @@ struct PadDma {
   }
 };
 
+// Padded-window mode of the head-dim <= 128 kernels (Hiera's windows that need padding,
+// hieradet.py:146): the operands stay in the image layout ([B, H, W, 3d] projection output,
+// [B, H, W, d] attention output) and every row of a window is reached through a row map, so no
+// partitioned copy exists.  Batch-head bh = (image * nW + window) * heads + head; the batch strides of
+// the launch are per IMAGE and the row strides per token.  A padded position reads a bias row (what
+// the projection gives for a zero input row) as q / k / v and a zero row as dO; as a query it is never
+// stored, as a key its dk / dv go to a compact buffer [B * P][..] in window_pad_colsum's row order.
+#define FL_WIN_MAXL 512  // window positions the LDS copy of the map holds
+struct WinArgs {
+  const int* row;        // [nW][L] token index y * W + x of window position l, -1 = padding
+  const int* padidx;     // [nW][L] compact row (within the image's P) of a padded position, -1 = real
+  const uint32_t* sets;  // [nW] bit s: positions 16 s .. 16 s + 15 hold a real token
+  int nW, P;             // windows / padded positions per image
+  const bf16* qpad; const bf16* kpad; const bf16* vpad;  // head 0 of the bias row's q / k / v thirds
+  const bf16* zrow;      // a row of zeros (dO of a padded query)
+  bf16* dkpad; bf16* dvpad; int64_t sdpad;  // compact padded-key gradients, row stride
+};
+
+// dma_tile_pad through a row map held in LDS (map[l] = token or -1): row l comes from
+// src + map[l] * ld, or from padsrc.  Same bytes in the same LDS image as dma_tile_pad on the
+// partitioned copy (rows past nrows clamp to the last one there too).
+template <int DP, int ROWS = 64, int NWV = FL_WAVES>
+__device__ __forceinline__ void dma_tile_pad_win(char* lds_tile, const bf16* src, const bf16* padsrc, const int* map,
+                                                 int64_t ld, int r0, int nrows, int w, int lane, int dvalid) {
+  using I = PadImg<DP, ROWS, NWV>;
+#pragma unroll
+  for (int i = 0; i < I::PPW_LO + (I::NHI ? 1 : 0); ++i) {
+    if (i == I::PPW_LO && w >= I::NHI) break;  // wave-uniform
+    const int piece = w + i * NWV;
+    const int slot = piece * 64 + lane;
+    const int row = slot / I::SPR, c = slot % I::SPR;
+    const int t = map[min(r0 + row, nrows - 1)];
+    const bf16* g = (t >= 0 ? src + t * (int)ld : padsrc) + (c < DP / 8 && c * 8 < dvalid ? c * 8 : 0);
+    lds_dma16(g, lds_tile + piece * 1024);
+  }
+}
+// dma_tile (the swizzled image) through the map
+template <int DP, int ROWS, int NWV = FL_WAVES, int SW = 0>
+__device__ __forceinline__ void dma_tile_win(char* lds_tile, const bf16* src, const bf16* padsrc, const int* map,
+                                             int64_t ld, int r0, int nrows, int w, int lane, int dvalid) {
+  using C = FlashCfg<DP, ROWS, NWV>;
+#pragma unroll
+  for (int i = 0; i < C::PPW; ++i) {
+    const int piece = w * C::PPW + i;
+    const int row = piece * C::RPP + lane / C::NCH;
+    const int pos = lane % C::NCH;
+    const int c = pos ^ swz_x<DP, SW>(row);
+    const int t = map[min(r0 + row, nrows - 1)];
+    const bf16* g = (t >= 0 ? src + t * (int)ld : padsrc) + (c * 8 < dvalid ? c * 8 : 0);
+    lds_dma16(g, lds_tile + piece * 1024);
+  }
+}
+
 // XCD-aware work order: workgroup `id` (x fastest) runs on XCD id % 8, so round-robin placed the
 // workgroups that re-read one (batch, head)'s operands -- the query blocks of a forward / dQ
 // launch, the key blocks of a dK/dV launch -- on 8 different L2s.  Here XCD j runs every x (and z)

@@ -106,6 +106,12 @@ SIGNATURES = {
     "s2h_window": [I, I, I, I, I, I, P, P, I, I, P],
     "s2h_window_pad": [I, I, I, I, I, I, P, P, P, P],
     "s2h_window_pad_colsum": [I, I, I, I, I, I, P, P, P],
+    "s2h_pad_rows_colsum": [I, I, I, P, P, P],
+    "s2h_window_map_len": [I, I, I],
+    "s2h_window_map": [I, I, I, P, L],
+    "s2h_flash_win_ok": [I, I, I, I, I, I, I],
+    "s2h_flash_win_fwd": [I, I, I, I, I, I, P, P, P, P, P, F, P],
+    "s2h_flash_win_bwd": [I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, F, P],
     "s2h_copy2d_batch": [I, P, P, P, P, P, P, P],
     "s2h_up2_add": [I, I, I, I, I, P, P, P, P],
     "s2h_pool2_sum": [I, I, I, I, I, P, P, I, P],
@@ -177,6 +183,7 @@ _LIB = None
 # entry points that do not return a hipError_t
 RESTYPES = {"s2h_attn_fwd_ws_bytes": c_int64, "s2h_attn_bwd_ws_bytes": c_int64, "s2h_attn_keep_words": c_int64,
             "s2h_attn_fwd_vfold_ws_bytes": c_int64,
+            "s2h_window_map_len": c_int64,
             "s2h_layernorm_bwd_ws_bytes": c_int64, "s2h_linear_dgrad_ln_bwd_ws_bytes": c_int64,
             "s2h_grad_defer_pending": c_int}
 

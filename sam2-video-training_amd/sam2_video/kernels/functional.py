@@ -853,6 +853,58 @@ def window_pad(y, ws, mod):
     return _WindowPad.apply(y, int(ws), mod)
 
 
+class _PadWindowAttention(torch.autograd.Function):
+    """Attention over the padded ws x ws windows of linear `mod`'s output y [B, H, W, 3 d], straight from
+    the image layout (ops.flash_win_fwd): equals window_unpartition(qkv_attention(window_pad(y))) bit
+    for bit with no partitioned copy of qkv, o, do or dqkv.  The flash kernels reach every window row
+    through a row map; padded positions read the bias row.  Backward: dqkv of the real tokens in the
+    image layout; the padded keys' dk / dv land in a compact buffer whose column sums go to the
+    linear's bias gradient (the padded queries' dq is exactly zero), accumulating like _WindowPad."""
+
+    @staticmethod
+    def forward(ctx, y, ws, nh, mod):
+        padrow = ops.cast(mod.compute_bias().contiguous().view(-1), torch.bfloat16)
+        scale = 1.0 / math.sqrt(y.shape[-1] // 3 // nh)
+        o, lse = ops.flash_win_fwd(y, ws, nh, padrow, scale)
+        ctx.ws, ctx.nh, ctx.mod, ctx.scale = ws, nh, mod, scale
+        ctx.save_for_backward(y, padrow, o, lse)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        y, padrow, o, lse = ctx.saved_tensors
+        B, H, W, d3 = y.shape
+        ws, d = ctx.ws, d3 // 3
+        dqkv, dpad = ops.flash_win_bwd(y, ws, ctx.nh, padrow, o, do.contiguous(), lse, ctx.scale)
+        gb = ctx.mod.grad_views()[1]
+        if gb is not None:
+            P = (-(-H // ws)) * ws * (-(-W // ws)) * ws - H * W
+            ops.pad_rows_colsum(dpad, B, P, gb.view(-1)[d:])
+        return dqkv, None, None, None
+
+
+def pad_window_map_enabled():
+    """S2H_HIERA_WIN_MAP=0: padded windows are partitioned (window_pad), attended and unpartitioned by
+    separate launches instead of the flash kernels reading the image layout through a row map"""
+    import os
+    return os.environ.get("S2H_HIERA_WIN_MAP", "1") == "1"
+
+
+def pad_window_attention_ok(y, ws, nh, mod):
+    """_PadWindowAttention's domain: the switch on, bf16 compute in the flash path, 16-B aligned rows,
+    per-launch extents within the kernels' 32-bit offsets (ops.flash_win_ok); else the caller keeps
+    window_pad + qkv_attention + window_unpartition"""
+    return (pad_window_map_enabled() and _ft.active() is None and mod.compute_bias() is not None
+            and ops.flash_win_ok(y, ws, nh))
+
+
+def pad_window_attention(y, ws, nh, mod):
+    """softmax(q k^T / sqrt(hd)) v within the zero-padded ws x ws windows of y = mod(x) [B, H, W, 3 d]
+    (padded positions = mod's bias) -> [B, H, W, d]"""
+    assert mod.compute_bias() is not None
+    return _PadWindowAttention.apply(y, int(ws), int(nh), mod)
+
+
 def window_partition(x, ws):
     return _WindowPartition.apply(x, int(ws))
 

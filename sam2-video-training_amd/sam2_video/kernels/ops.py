@@ -944,6 +944,109 @@ def window_pad_colsum(win, ws, B, H, W, out):
     return out
 
 
+# Padded-window attention straight from the image layout (csrc/flash.hip s2h_flash_win_fwd): the row
+# map of a geometry is built (and range-checked) by the library on the host, uploaded once per device
+# and kept for the life of the process, like the zero row the backward reads as a padded query's dO.
+_WIN_MAPS = {}
+_WIN_ZERO = {}
+
+
+def window_map_host(H, W, ws):
+    """the host row map of geometry (H, W, ws) as numpy int32 arrays (row [nW, L], padidx [nW, L],
+    sets [nW]): row = token index y * W + x of window position l = iy * ws + ix or -1 for padding,
+    padidx = the padded position's row in window_pad_colsum's order or -1, sets = bit s set when
+    positions 16 s .. 16 s + 15 hold a token (s2h_window_map; raises if an entry is out of range)"""
+    n = int(lib().s2h_window_map_len(int(H), int(W), int(ws)))
+    if n <= 0:
+        raise ValueError(f"window map of ({H}, {W}, {ws})")
+    buf = np.empty(n, dtype=np.int32)
+    call("s2h_window_map", int(H), int(W), int(ws), buf.ctypes.data, n)
+    nW, L = (-(-H // ws)) * (-(-W // ws)), ws * ws
+    return buf[:nW * L].reshape(nW, L), buf[nW * L:2 * nW * L].reshape(nW, L), buf[2 * nW * L:]
+
+
+def window_map(H, W, ws, device):
+    """the device copy of s2h_window_map(H, W, ws) (int32, [row | padidx | sets]); first use of a
+    geometry must come before a graph capture (the warm-up steps do)"""
+    d = _device_of(device)
+    key = (int(H), int(W), int(ws), d)
+    t = _WIN_MAPS.get(key)
+    if t is None:
+        row, pad, sets = window_map_host(H, W, ws)
+        t = _persistent_alloc("window_map", row.size + pad.size + sets.size, torch.int32, d)
+        t.copy_(torch.from_numpy(np.concatenate([row.ravel(), pad.ravel(), sets])))
+        _WIN_MAPS[key] = t
+    return t
+
+
+def _win_zero_row(n, device):
+    d = _device_of(device)
+    t = _WIN_ZERO.get(d)
+    if t is None or t.numel() < n:
+        t = _persistent_alloc("window_zero_row", max(n, 128), torch.bfloat16, d)
+        t.zero_()
+        _WIN_ZERO[d] = t
+    return t
+
+
+def flash_win_ok(qkv, ws, nh):
+    """the padded-window mode takes qkv [B, H, W, 3 d] (d = nh heads x hd): bf16, contiguous, the
+    flash domain, 16-B aligned rows, per-image extents within the kernels' 32-bit offsets, enough
+    batch-heads that the partitioned launches would run without a key split"""
+    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.is_contiguous()):
+        return False
+    B, H, W, d3 = qkv.shape
+    if d3 % (3 * nh) or qkv.data_ptr() % 16:
+        return False
+    return bool(lib().s2h_flash_win_ok(BF16, B, H, W, int(ws), int(nh), d3 // 3 // nh))
+
+
+def flash_win_fwd(qkv, ws, nh, padrow, scale):
+    """qkv [B, H, W, 3 d] bf16, padrow [3 d] bf16 (the projection's bias) -> o [B, H, W, d], lse
+    [B * nW * nh, L] (+inf at padded positions)"""
+    B, H, W, d3 = qkv.shape
+    d = d3 // 3
+    nW, L = (-(-H // ws)) * (-(-W // ws)), ws * ws
+    assert padrow.dtype == torch.bfloat16 and padrow.numel() == d3 and padrow.is_contiguous()
+    m = window_map(H, W, ws, qkv.device)
+    _win_zero_row(d // nh, qkv.device)  # the backward's, allocated outside any capture
+    o = torch.empty(B, H, W, d, device=qkv.device, dtype=qkv.dtype)
+    lse = torch.empty(B * nW * nh, L, device=qkv.device, dtype=torch.float32)
+    _dev(qkv, padrow, o, lse)
+    call("s2h_flash_win_fwd", B, H, W, int(ws), int(nh), d // nh, ptr(qkv), ptr(padrow), ptr(m), ptr(o), ptr(lse),
+         float(scale), stream())
+    return o, lse
+
+
+def flash_win_bwd(qkv, ws, nh, padrow, o, do, lse, scale):
+    """-> dqkv [B, H, W, 3 d] (dq | dk | dv of the real tokens), dpad [B * P, 2 d] (dk | dv of the
+    padded keys, P per image, window_pad_colsum's order)"""
+    B, H, W, d3 = qkv.shape
+    d = d3 // 3
+    nhw, nww = -(-H // ws), -(-W // ws)
+    nW, L, P = nhw * nww, ws * ws, nhw * ws * nww * ws - H * W
+    assert do.is_contiguous() and do.shape == o.shape and do.dtype == o.dtype
+    m = window_map(H, W, ws, qkv.device)
+    z = _win_zero_row(d // nh, qkv.device)
+    dqkv = torch.empty_like(qkv)
+    dpad = torch.empty(B * P, 2 * d, device=qkv.device, dtype=qkv.dtype)
+    di = torch.empty(B * nW * nh * L, device=qkv.device, dtype=torch.float32)
+    _dev(qkv, padrow, o, do, lse, dqkv, dpad)
+    call("s2h_flash_win_bwd", B, H, W, int(ws), int(nh), d // nh, ptr(qkv), ptr(padrow), ptr(z), ptr(m), ptr(o), ptr(do),
+         ptr(dqkv), ptr(dpad), ptr(lse), ptr(di), float(scale), stream())
+    return dqkv, dpad
+
+
+def pad_rows_colsum(dpad, B, P, out):
+    """out (fp32 [C]) += the column sums of dpad [B * P, C] (bf16): window_pad_colsum over compact rows"""
+    C = dpad.shape[-1]
+    assert out.dtype == torch.float32 and out.numel() == C and out.is_contiguous() and dpad.is_contiguous()
+    assert dpad.dtype == torch.bfloat16 and dpad.shape[0] == B * P
+    _dev(dpad, out)
+    call("s2h_pad_rows_colsum", B, P, C, ptr(dpad), ptr(out), stream())
+    return out
+
+
 def window_unpartition(win, ws, B, H, W, out=None, accumulate=False):
     C = win.shape[-1]
     if out is None:

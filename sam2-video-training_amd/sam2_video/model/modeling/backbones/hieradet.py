@@ -98,11 +98,19 @@ class MultiScaleBlock(nn.Module):
             # projection of a zero-padded row is its bias, so project the real tokens only, partition
             # the projection with bias rows, and project back after unpartition -- the qkv and proj
             # GEMMs (and their backward) run on H*W instead of the padded rows (0.58x at 512^2)
+            # -- and the flash kernels read that projection in place through the window row map
+            # (S2H_HIERA_WIN_MAP=0, or outside the mode's domain: partition with bias rows, attend,
+            # unpartition as separate launches)
             a = self.attn
-            qkvw = FN.window_pad(a.qkv(xn), ws, a.qkv)
-            nwin, d, nh = qkvw.shape[0], a.dim_out, a.num_heads
-            o = FN.qkv_attention(qkvw.view(nwin, ws * ws, 3, nh, d // nh))
-            y = a.proj(FN.window_unpartition(o.reshape(nwin, ws, ws, d), ws, B, H, W))
+            d, nh = a.dim_out, a.num_heads
+            qkv = a.qkv(xn)
+            if FN.pad_window_attention_ok(qkv, ws, nh, a.qkv):
+                y = a.proj(FN.pad_window_attention(qkv, ws, nh, a.qkv))
+            else:
+                qkvw = FN.window_pad(qkv, ws, a.qkv)
+                nwin = qkvw.shape[0]
+                o = FN.qkv_attention(qkvw.view(nwin, ws * ws, 3, nh, d // nh))
+                y = a.proj(FN.window_unpartition(o.reshape(nwin, ws, ws, d), ws, B, H, W))
         else:
             xw = FN.window_partition(xn, ws) if ws > 0 else xn
             y = self.attn(xw)
