@@ -752,6 +752,39 @@ int s2h_mask_sweep(int N, int hi, int wi, int H, int W, const float* low, int Nc
  * scratch.  Integer arithmetic in a fixed order, every device loop bounded; sizes as for s2h_mask_export. */
 int s2h_rle_transitions(int Ncat, int H, int W, const uint64_t* bits, int capacity, int* hdr, int* trans,
                         int* work, hipStream_t st);
+/* ---- clip loading (reference sam2_video/data/dataset.py:103-110 and :139-179, the torchvision transforms and
+ * the pycocotools decode; csrc/preproc.hip).  Both entries are pure functions of their inputs: integer
+ * arithmetic, no atomics, no shared memory, no host round trip, every device loop bounded by a table size.
+ *
+ * Pillow's Image.resize on uint8 RGB, the crop and the normalisation in one call.  src [F, H, W, 3] uint8, all
+ * frames one size; out [F, 3, Sh, Sw] fp32.  The filter is in the tables, built on the host per axis (Pillow's
+ * precompute_coeffs and normalize_coeffs_8bpc): x_min / x_cnt int32 [Sw] = first source column and tap count of
+ * output column o, x_coef int32 [Sw, kx] = the weights * 2^22, rounded; y_* likewise over rows, [Sh] and
+ * [Sh, ky].  A cropped output passes only the table rows of its window.  Two passes in Pillow's order:
+ * mid[f][r][o][c] = clip8((sum_k x_coef[o][k] * src[f][row0 + r][x_min[o] + k][c] + 2^21) >> 22) for the nrows
+ * source rows from row0 (the rows the vertical taps read: every y_min[o] >= row0 and y_min[o] + y_cnt[o] <=
+ * row0 + nrows), then the same sum down the columns of mid; out = lut[c][value], lut [3, 256] fp32 filled by
+ * the host with the normalised value of every byte.  scratch: F * nrows * Sw * 3 bytes (mid).  A tap window
+ * that leaves the line, or is longer than its table row, is cut to what is inside: nothing outside src or
+ * scratch is read.  1 <= kx, ky <= 64 (hipErrorInvalidValue otherwise, as for every limit here);
+ * 1 <= H, W, Sh, Sw <= 16384; 0 <= row0, row0 + nrows <= H; F * H * W * 3, F * nrows * Sw * 3 and
+ * F * 3 * Sh * Sw < 2^31 - 256. */
+int s2h_resample_u8_norm(int F, int H, int W, const uint8_t* src, int Sw, int kx, const int* x_min,
+                         const int* x_cnt, const int* x_coef, int Sh, int ky, const int* y_min, const int* y_cnt,
+                         const int* y_coef, int row0, int nrows, const float* lut, uint8_t* scratch, float* out,
+                         hipStream_t st);
+/* Category masks of F frames from COCO RLE, nearest-resized and cropped, without the dense H x W masks.
+ * run_off [A + 1] / run_end as for s2h_rle_decode, the A annotations of all frames back to back, every one
+ * of an H x W image; ann_cat [A] int32 = the category index of an annotation, outside [0, N) = skipped;
+ * frame_off [F + 1] = the annotations of frame f are [frame_off[f], frame_off[f + 1]) (cut to [0, A]).
+ * row_map [Sh] / col_map [Sw] int32 = the source row / column of each output row / column (the nearest resize
+ * and the crop folded in by the host; values in [0, H) / [0, W)).  out [F, N, Sh, Sw] uint8 of 0 / 1, every
+ * element written: out[f][n][y][x] = OR over frame f's annotations of category n of k & 1, k = the number of
+ * the annotation's run_end <= col_map[x] * H + row_map[y] (binary search, at most 32 steps).
+ * 0 <= N <= 64; 1 <= H, W, Sh, Sw <= 16384; H * W and F * N * Sh * Sw < 2^31 - 256. */
+int s2h_rle_catmasks(int F, int N, int H, int W, int A, const int* run_off, const int* run_end,
+                     const int* ann_cat, const int* frame_off, int Sh, int Sw, const int* row_map,
+                     const int* col_map, uint8_t* out, hipStream_t st);
 /* The first upscaling step in one pass (mask_decoder.py:105-106, bf16, Co = 64): pre = the s2h_convt2_store
  * values, y / mean / rstd = LayerNorm2d(pre) over the channels (gamma, beta, eps; the values of
  * s2h_layernorm_fwd), post = gelu(y) (as s2h_act_fwd rounds it); mean / rstd [B * 2H * 2W] fp32. */

@@ -13,6 +13,12 @@ pycocotools (not installed here): same classes, constructor arguments and item l
   collated by data.synthetic.sam2_collate_fn into BatchedVideoDatapoint.
 
 Host-side work (the reference runs it in DataLoader workers as well).
+
+`preprocess_on_device: true` in the data section moves everything after the image decode to the device: items
+carry the decoded uint8 frame and the annotations' RLE run boundaries instead of the finished tensors
+(data/preprocess.py turns them into the same tensors with HIP kernels, bit for bit), the per-image cache holds
+the runs instead of dense masks, and a clip also carries frame 0's dense masks from the host path below,
+which the prompt stage samples its clicks from on the host.
 """
 from __future__ import annotations
 
@@ -64,6 +70,12 @@ def load_image(path: str, size: int) -> torch.Tensor:
     return (x - mean) / std
 
 
+def load_frame(path: str) -> torch.Tensor:
+    """RGB image -> uint8 [H, W, 3] as decoded: what load_image resizes"""
+    from PIL import Image
+    return torch.from_numpy(np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8).copy())
+
+
 def resize_mask(m: np.ndarray, size: int) -> torch.Tensor:
     """uint8 mask [H, W] -> bool [size, size]: nearest resize of the short side, center crop
     (dataset.py:166-169)"""
@@ -105,11 +117,18 @@ class COCOImageDataset(torch.utils.data.Dataset):
             self.video_to_images[vid].sort(key=lambda x: x.get("order_in_video", 0))
         self.image_id_to_idx = {img["id"]: i for i, img in enumerate(self.images)}
         self.mask_cache: Dict[int, torch.Tensor] = {}
+        self.preprocess_on_device = bool(_cfg(config, "preprocess_on_device", False))
+        self.runs_cache: Dict[int, Any] = {}
 
     def _load_gt_masks_for_image(self, image_id: int) -> torch.Tensor:
         """dataset.py:139-179: [num_categories, S, S] bool, instances of a category OR-ed"""
         if image_id in self.mask_cache:
             return self.mask_cache[image_id]
+        masks = self._build_gt_masks(image_id)
+        self.mask_cache[image_id] = masks
+        return masks
+
+    def _build_gt_masks(self, image_id: int) -> torch.Tensor:
         S = self.image_size
         masks = torch.zeros((self.num_categories, S, S), dtype=torch.bool)
         for ann in self.image_id_to_annotations.get(image_id, []):
@@ -120,14 +139,66 @@ class COCOImageDataset(torch.utils.data.Dataset):
             if ci is None or ci >= self.num_categories:
                 continue
             masks[ci] |= resize_mask(_rle.decode(seg), S)
-        self.mask_cache[image_id] = masks
         return masks
+
+    def _load_runs_for_image(self, image_id: int):
+        """the annotations _load_gt_masks_for_image would OR, as run boundaries: (H, W, run_off int32 [A + 1],
+        run_end int32 [R], ann_cat int32 [A], any mask pixel left after resize and crop); H = W = 0 without
+        annotations.  Cached per image: a few KB instead of the dense [N, S, S] masks."""
+        hit = self.runs_cache.get(image_id)
+        if hit is not None:
+            return hit
+        from ..kernels import ops
+        counts, cats, size = [], [], None
+        for ann in self.image_id_to_annotations.get(image_id, []):
+            seg, cat_id = ann.get("segmentation"), ann.get("category_id")
+            if seg is None or cat_id is None:
+                continue
+            ci = self.catid_to_idx.get(cat_id)
+            if ci is None or ci >= self.num_categories:
+                continue
+            h, w, cnts = _rle.counts_of(seg)
+            if size is None:
+                size = (h, w)
+            elif size != (h, w):
+                raise ValueError(f"image {image_id}: annotations of sizes {size} and {(h, w)}; the device loader "
+                                 "needs one size per image (preprocess_on_device: false takes any)")
+            counts.append(cnts)
+            cats.append(ci)
+        H, W = size or (0, 0)
+        run_off, run_end = ops.rle_runs(counts, H, W)
+        nonempty = False
+        if counts:
+            rows, cols = ops.nearest_maps(H, W, self.image_size)
+            nonempty = any(_rle.runs_hit_grid(run_end[run_off[a]:run_off[a + 1]], H, rows, cols)
+                           for a in range(len(counts)))
+        hit = (H, W, torch.from_numpy(run_off), torch.from_numpy(run_end), torch.tensor(cats, dtype=torch.int32),
+               nonempty)
+        self.runs_cache[image_id] = hit
+        return hit
 
     def __len__(self):
         return len(self.images)
 
+    def _raw_item(self, idx):
+        """the device loader's item: the decoded frame and the runs; the same replacement rule, decided from
+        the runs (rle.runs_hit_grid) instead of a dense mask"""
+        for _ in range(len(self.images)):
+            info = self.images[idx]
+            H, W, run_off, run_end, ann_cat, nonempty = self._load_runs_for_image(info["id"])
+            if nonempty:
+                frame = load_frame(info["path"])
+                if tuple(frame.shape[:2]) != (H, W):
+                    raise ValueError(f"image {info['id']}: the file is {tuple(frame.shape[:2])}, its annotations "
+                                     f"{(H, W)}; the device loader needs them equal")
+                return {"frame": frame, "runs": (run_off, run_end, ann_cat), "index": idx}
+            idx = (idx + 1) % len(self.images)
+        raise RuntimeError("every image of the dataset has empty masks")
+
     def __getitem__(self, idx):
         """dataset.py:184-216 (an image without any mask pixel is replaced by the next one)"""
+        if self.preprocess_on_device:
+            return self._raw_item(idx)
         for _ in range(len(self.images)):
             info = self.images[idx]
             masks = self._load_gt_masks_for_image(info["id"])
@@ -159,6 +230,11 @@ class VideoDataset(torch.utils.data.Dataset):
 
     def __getitem__(self, idx):
         items = [self.image_dataset[i] for i in self.clip_indices[idx]["image_indices"]]
+        if self.image_dataset.preprocess_on_device:
+            # frame 0's dense masks by the host path (not cached): the prompt stage reads them on the host
+            ds = self.image_dataset
+            masks0 = ds._build_gt_masks(ds.images[items[0]["index"]]["id"])
+            return {"frames": [it["frame"] for it in items], "runs": [it["runs"] for it in items], "masks0": masks0}
         return {"images": torch.stack([it["image"] for it in items]),
                 "masks": torch.stack([it["masks"] for it in items])}
 

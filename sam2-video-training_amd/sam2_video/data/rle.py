@@ -67,8 +67,8 @@ def _as_rle(rle: Union[Dict, str]) -> Dict:
     return rle
 
 
-def decode(rle: Union[Dict, str]) -> np.ndarray:
-    """RLE (compressed or uncompressed counts) -> uint8 mask [h, w]"""
+def counts_of(rle: Union[Dict, str]):
+    """RLE dict (compressed or uncompressed counts) -> (h, w, run lengths as a list)"""
     rle = _as_rle(rle)
     h, w = (int(v) for v in rle["size"])
     cnts = rle["counts"]
@@ -76,6 +76,12 @@ def decode(rle: Union[Dict, str]) -> np.ndarray:
         cnts = cnts.decode("ascii")
     if isinstance(cnts, str):
         cnts = counts_from_string(cnts)
+    return h, w, list(cnts)
+
+
+def decode(rle: Union[Dict, str]) -> np.ndarray:
+    """RLE (compressed or uncompressed counts) -> uint8 mask [h, w]"""
+    h, w, cnts = counts_of(rle)
     cnts = np.asarray(cnts, dtype=np.int64)
     if cnts.sum() != h * w:
         raise ValueError(f"RLE counts cover {int(cnts.sum())} pixels, mask has {h * w}")
@@ -111,6 +117,37 @@ def counts_from_transitions(trans, n_pixels: int) -> List[int]:
 def from_transitions(trans, h: int, w: int) -> Dict:
     """run boundaries of an [h, w] mask -> compressed RLE dict (the dict `encode` gives for that mask)"""
     return {"size": [int(h), int(w)], "counts": counts_to_string(counts_from_transitions(trans, int(h) * int(w)))}
+
+
+_GRID_POS: Dict = {}
+
+
+def grid_positions(H: int, rows, cols) -> np.ndarray:
+    """the column-major positions c * H + r of a sampling grid (rows x cols of an image of height H), sorted;
+    kept per grid (a dataset has one or two)"""
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    cols = np.ascontiguousarray(cols, dtype=np.int64)
+    key = (int(H), rows.tobytes(), cols.tobytes())
+    pos = _GRID_POS.get(key)
+    if pos is None:
+        if len(_GRID_POS) >= 16:
+            _GRID_POS.clear()
+        pos = np.sort((cols[:, None] * int(H) + rows[None, :]).reshape(-1))
+        _GRID_POS[key] = pos
+    return pos
+
+
+def runs_hit_grid(run_end, H: int, rows, cols) -> bool:
+    """does any sampled position c * H + r (r in rows, c in cols) of a mask of height H fall in a set run?
+    run_end: the cumulative sums of the mask's counts (ops.rle_runs); run k covers [run_end[k - 1], run_end[k])
+    and the odd runs are set.  Decided from the runs alone: two searches in the sorted positions per mask."""
+    end = np.asarray(run_end, dtype=np.int64).reshape(-1)
+    if end.size < 2:
+        return False
+    pos = grid_positions(H, rows, cols)
+    lo = np.searchsorted(pos, end[0:-1:2], side="left")  # starts of the set runs 1, 3, ...
+    hi = np.searchsorted(pos, end[1::2], side="left")
+    return bool((hi > lo[:hi.size]).any())
 
 
 def area(rle) -> int:

@@ -1400,6 +1400,179 @@ def rle_decode(counts_list, H, W, device="cuda"):
     return mask
 
 
+# ------------------------------------------------------------------------------------------- clip loading
+RS_BITS = 22       # csrc/resample_u8.h: Pillow's PRECISION_BITS
+RS_MAX_TAPS = 64   # taps per output sample
+RS_MAX_SIDE = 16384
+RS_MAX_CATS = 64
+
+
+def _pil_bilinear(x):
+    x = -x if x < 0.0 else x
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def _pil_bicubic(x):
+    a = -0.5
+    x = -x if x < 0.0 else x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+_PIL_FILTERS = {"bilinear": (_pil_bilinear, 1.0), "bicubic": (_pil_bicubic, 2.0)}
+_TAPS = {}
+
+
+def resample_taps(in_size, out_size, filter="bilinear"):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc (libImaging/Resample.c) for one axis, in Python double
+    arithmetic and in Pillow's order of operations -> (xmin int32 [out], cnt int32 [out], coef int32 [out, ksize])
+    numpy: output sample o reads cnt[o] source samples from xmin[o], weighted by coef[o] / 2^22 (rows padded
+    with zeros).  filter "bilinear" (support 1) or "bicubic" (support 2, a = -0.5).  Cached."""
+    key = (int(in_size), int(out_size), filter)
+    hit = _TAPS.get(key)
+    if hit is not None:
+        return hit
+    in_size, out_size = key[0], key[1]
+    if filter not in _PIL_FILTERS:
+        raise ValueError(f"filter must be one of {sorted(_PIL_FILTERS)}, got {filter!r}")
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"sizes must be positive, got {in_size} -> {out_size}")
+    f, support = _PIL_FILTERS[filter]
+    scale = in_size / out_size
+    fs = scale if scale >= 1.0 else 1.0
+    sup = support * fs
+    ksize = int(math.ceil(sup)) * 2 + 1
+    ss = 1.0 / fs
+    xmin = np.zeros(out_size, np.int32)
+    cnt = np.zeros(out_size, np.int32)
+    coef = np.zeros((out_size, ksize), np.int32)
+    for o in range(out_size):
+        center = (o + 0.5) * scale
+        lo = max(int(center - sup + 0.5), 0)
+        n = min(int(center + sup + 0.5), in_size) - lo
+        w = [f((k + lo - center + 0.5) * ss) for k in range(n)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        for k in range(n):
+            v = w[k] / ww if ww != 0.0 else w[k]
+            coef[o, k] = int(-0.5 + v * (1 << RS_BITS)) if v < 0 else int(0.5 + v * (1 << RS_BITS))
+        xmin[o], cnt[o] = lo, n
+    for a in (xmin, cnt, coef):
+        a.setflags(write=False)
+    _TAPS[key] = (xmin, cnt, coef)
+    return _TAPS[key]
+
+
+_DEV_TABLES = {}
+
+
+def _dev_table(key, device, make):
+    """a small host-built int32 / fp32 table on `device`, uploaded once per key"""
+    k = (key, str(device))
+    t = _DEV_TABLES.get(k)
+    if t is None:
+        t = _DEV_TABLES[k] = tuple(torch.from_numpy(np.array(a, order="C")).to(device) for a in make())
+    return t
+
+
+def norm_lut(mean, std):
+    """[3, 256] fp32: the normalised value of every byte, by the torch expressions the host loaders use
+    (data/dataset.py load_image, predictor._load_frames): v.float() / 255, then (x - mean) / std"""
+    x = torch.arange(256, dtype=torch.uint8).view(1, 256).expand(3, 256).contiguous().float().div_(255.0)
+    m = torch.tensor(tuple(float(v) for v in mean)).view(3, 1)
+    s = torch.tensor(tuple(float(v) for v in std)).view(3, 1)
+    return ((x - m) / s).contiguous()
+
+
+def resample_u8_norm(frames_u8, out_hw, crop_top_left=(0, 0), filter="bilinear", mean=(0.485, 0.456, 0.406),
+                     std=(0.229, 0.224, 0.225), crop_hw=None, out=None):
+    """PIL `Image.resize(out_hw, filter)`, `crop` and the normalisation of F uint8 RGB frames
+    (s2h_resample_u8_norm): frames_u8 [F, H, W, 3] uint8 on the device -> [F, 3, ch, cw] fp32, bit for bit what
+    the host computes.  out_hw = (h, w) of the resized image, crop_top_left = (top, left) and crop_hw = (ch, cw)
+    of the window kept (default: the rest of the image)."""
+    assert frames_u8.dim() == 4 and frames_u8.shape[-1] == 3 and frames_u8.dtype == torch.uint8
+    assert frames_u8.is_contiguous()
+    _dev(frames_u8)
+    F, H, W, _ = frames_u8.shape
+    nh, nw = (int(v) for v in out_hw)
+    top, left = (int(v) for v in crop_top_left)
+    ch, cw = (nh - top, nw - left) if crop_hw is None else (int(v) for v in crop_hw)
+    if not (0 <= top and 0 <= left and ch >= 1 and cw >= 1 and top + ch <= nh and left + cw <= nw):
+        raise ValueError(f"crop ({top}, {left}) + ({ch}, {cw}) is outside the resized image ({nh}, {nw})")
+    xm, xc, xk = resample_taps(W, nw, filter)
+    ym, yc, yk = resample_taps(H, nh, filter)
+    kx, ky = xk.shape[1], yk.shape[1]
+    if kx > RS_MAX_TAPS or ky > RS_MAX_TAPS:
+        raise ValueError(f"{H} x {W} -> {nh} x {nw} ({filter}) needs {max(kx, ky)} taps, at most {RS_MAX_TAPS}")
+    ymw, ycw = ym[top:top + ch], yc[top:top + ch]
+    row0 = int(ymw.min())
+    nrows = int((ymw + ycw).max()) - row0
+    dev = frames_u8.device
+    tx = _dev_table(("taps", W, nw, filter, left, cw), dev, lambda: (xm[left:left + cw], xc[left:left + cw],
+                                                                      xk[left:left + cw]))
+    ty = _dev_table(("taps", H, nh, filter, top, ch), dev, lambda: (ymw, ycw, yk[top:top + ch]))
+    mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    lut, = _dev_table(("lut", mean, std), dev, lambda: (norm_lut(mean, std).numpy(),))
+    if out is None:
+        out = torch.empty(F, 3, ch, cw, device=dev, dtype=torch.float32)
+    assert out.shape == (F, 3, ch, cw) and out.dtype == torch.float32 and out.is_contiguous() and out.device == dev
+    scratch = torch.empty(max(1, F * nrows * cw * 3), device=dev, dtype=torch.uint8)
+    call("s2h_resample_u8_norm", F, H, W, ptr(frames_u8), cw, kx, ptr(tx[0]), ptr(tx[1]), ptr(tx[2]), ch, ky,
+         ptr(ty[0]), ptr(ty[1]), ptr(ty[2]), row0, nrows, ptr(lut), ptr(scratch), ptr(out), stream())
+    return out
+
+
+_NEAREST = {}
+
+
+def nearest_maps(H, W, S):
+    """(row_map int32 [S], col_map int32 [S]) numpy: the source row / column of every output row / column of
+    data/dataset.py resize_mask on an H x W mask -- F.interpolate(mode="nearest") to the short-side-S size (its
+    index rule, taken from torch itself on an arange), then the center crop.  Cached."""
+    key = (int(H), int(W), int(S))
+    hit = _NEAREST.get(key)
+    if hit is None:
+        from ..data.dataset import center_crop_box, resized_hw
+        H, W, S = key
+        nh, nw = resized_hw(H, W, S)
+        top, left = center_crop_box(nh, nw, S, S)
+        interp = torch.nn.functional.interpolate
+        rows = interp(torch.arange(H, dtype=torch.float32)[None, None], size=nh, mode="nearest")[0, 0]
+        cols = interp(torch.arange(W, dtype=torch.float32)[None, None], size=nw, mode="nearest")[0, 0]
+        hit = (rows[top:top + S].to(torch.int32).numpy().copy(), cols[left:left + S].to(torch.int32).numpy().copy())
+        for a in hit:
+            a.setflags(write=False)
+        _NEAREST[key] = hit
+    return hit
+
+
+def rle_catmasks(run_off, run_end, ann_cat, frame_off, H, W, row_map, col_map, num_categories, out=None):
+    """category masks of F frames straight from COCO RLE run boundaries (s2h_rle_catmasks): run_off [A + 1] /
+    run_end as ops.rle_runs gives them for the annotations of all frames back to back, ann_cat [A] the category
+    index of each (outside [0, num_categories) = skipped), frame_off [F + 1] the annotations per frame (CSR),
+    row_map [Sh] / col_map [Sw] the source row / column of every output row / column (ops.nearest_maps); all
+    int32 on the device.  -> bool [F, num_categories, Sh, Sw]: what dataset.resize_mask(rle.decode(.)) OR-ed
+    per category gives."""
+    for t in (run_off, run_end, ann_cat, frame_off, row_map, col_map):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
+    _dev(run_off, run_end, ann_cat, frame_off, row_map, col_map)
+    A, F, N = ann_cat.numel(), frame_off.numel() - 1, int(num_categories)
+    assert run_off.numel() == A + 1 and F >= 0
+    if not 0 <= N <= RS_MAX_CATS:
+        raise ValueError(f"num_categories {N} is outside [0, {RS_MAX_CATS}]")
+    Sh, Sw = row_map.numel(), col_map.numel()
+    if out is None:
+        out = torch.empty(F, N, Sh, Sw, device=frame_off.device, dtype=torch.bool)
+    assert out.shape == (F, N, Sh, Sw) and out.dtype == torch.bool and out.is_contiguous()
+    call("s2h_rle_catmasks", F, N, int(H), int(W), A, ptr(run_off), ptr(run_end), ptr(ann_cat), ptr(frame_off), Sh, Sw,
+         ptr(row_map), ptr(col_map), ptr(out), stream())
+    return out
+
+
 def morph_rect(mask, op, y_win, x_win, out=None):
     """rectangular dilation (op "dilate" / 0) or erosion ("erode" / 1) of byte masks [N, H, W]
     (s2h_morph_rect): out(y, x) = OR / AND of mask(y + dy, x + dx) over dy in [y_win[0], y_win[1]] and dx in

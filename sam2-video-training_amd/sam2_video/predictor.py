@@ -78,6 +78,47 @@ def _load_frames(video_path, image_size):
     return (x - mean) / std, H, W
 
 
+def _load_frames_device(video_path, image_size, device, chunk, keep_on_device):
+    """_load_frames with everything after the decode on the device: the uint8 frames are uploaded `chunk` at a
+    time and resized by ops.resample_u8_norm with Pillow's bicubic taps (Image.resize's default filter) to
+    S x S, the same fp32 values bit for bit.  keep_on_device: the result stays on `device`; otherwise every
+    chunk is copied back and the result is the host tensor _load_frames returns."""
+    from PIL import Image
+    if isinstance(video_path, torch.Tensor) and video_path.is_floating_point():
+        return _load_frames(video_path, image_size)
+    if isinstance(video_path, (str, os.PathLike)):
+        names = [p for p in os.listdir(video_path) if os.path.splitext(p)[-1].lower() in (".jpg", ".jpeg")]
+        names.sort(key=lambda p: int(os.path.splitext(p)[0]))
+        if not names:
+            raise RuntimeError(f"no JPEG frames found in {video_path}")
+        T = len(names)
+
+        def frame(t):
+            return np.asarray(Image.open(os.path.join(video_path, names[t])).convert("RGB"), dtype=np.uint8)
+    else:
+        arr = video_path.numpy() if isinstance(video_path, torch.Tensor) else np.asarray(video_path)
+        T = len(arr)
+
+        def frame(t):
+            return np.ascontiguousarray(arr[t].astype(np.uint8))
+    S = int(image_size)
+    out = torch.empty(T, 3, S, S, dtype=torch.float32, device=device if keep_on_device else "cpu")
+    H = W = None
+    for lo in range(0, T, chunk):
+        hi = min(T, lo + chunk)
+        raw = np.stack([frame(t) for t in range(lo, hi)])  # [F, H, W, 3]
+        if H is None:
+            H, W = raw.shape[1:3]
+        elif raw.shape[1:3] != (H, W):
+            raise ValueError(f"frames {lo}..{hi - 1} are {raw.shape[1:3]}, the first ones {(H, W)}")
+        dev = torch.from_numpy(raw).to(device, non_blocking=True)
+        if keep_on_device:
+            ops.resample_u8_norm(dev, (S, S), (0, 0), "bicubic", IMAGENET_MEAN, IMAGENET_STD, out=out[lo:hi])
+        else:
+            out[lo:hi] = ops.resample_u8_norm(dev, (S, S), (0, 0), "bicubic", IMAGENET_MEAN, IMAGENET_STD)
+    return out, H, W
+
+
 def _connected_components(binary):
     """8-connected components -> (labels, per-pixel component area); host scipy (the CPU path of
     fill_holes_in_mask_scores; GPU tensors take get_connected_components / ops.fill_holes)"""
@@ -242,7 +283,7 @@ class SAM2VideoPredictor:
     def __init__(self, model, fill_hole_area: int = 0, non_overlap_masks: bool = False,
                  clear_non_cond_mem_around_input: bool = False, add_all_frames_to_correct_as_cond: bool = False,
                  binarize_mask_from_pts_for_mem_enc: bool = True, maskmem_storage_dtype=torch.bfloat16,
-                 frame_chunk: int = 8, postprocess_on_device: bool = True):
+                 frame_chunk: int = 8, postprocess_on_device: bool = True, preprocess_on_device: bool = False):
         if model.arena is None:
             raise RuntimeError("call SAM2Model.load(device) before building a predictor")
         object.__setattr__(self, "model", model)
@@ -255,6 +296,8 @@ class SAM2VideoPredictor:
         self.frame_chunk = max(1, int(frame_chunk))
         # hole filling by the HIP kernels (stream-ordered, no copy); False: the host scipy path (A/B, tests)
         self.postprocess_on_device = bool(postprocess_on_device)
+        # resize + normalise the video's frames with the HIP kernels (uint8 upload); False: PIL on the host
+        self.preprocess_on_device = bool(preprocess_on_device)
         # keep every mask token's low-res logits of the three-mask heads in the frame outputs
         self.keep_multimask_candidates = False
         model.eval()
@@ -287,7 +330,11 @@ class SAM2VideoPredictor:
         # weights may have been loaded into a submodule in place (the reference's
         # _load_finetuned_weights_into_predictor): refresh the bf16 compute shadow
         m.arena.refresh_shadow()
-        images, H, W = _load_frames(video_path, m.image_size)
+        if self.preprocess_on_device:
+            images, H, W = _load_frames_device(video_path, m.image_size, device, self.frame_chunk,
+                                               keep_on_device=not offload_video_to_cpu)
+        else:
+            images, H, W = _load_frames(video_path, m.image_size)
         state = {
             "images": images if offload_video_to_cpu else images.to(device),
             "num_frames": images.shape[0], "video_height": H, "video_width": W, "device": device,
@@ -761,7 +808,8 @@ UPSTREAM_MULTIMASK_OVERRIDES = {
 
 def build_sam2_video_predictor(config_file, ckpt_path=None, device="cuda", mode="eval", hydra_overrides_extra=(),
                                apply_postprocessing=True, vos_optimized=False, compute_dtype="bf16", image_size=None,
-                               multimask: bool = False, postprocess_on_device: bool = True, **kwargs):
+                               multimask: bool = False, postprocess_on_device: bool = True,
+                               preprocess_on_device: bool = False, **kwargs):
     """upstream sam2.build_sam.build_sam2_video_predictor: the SAM2.1 model of `config_file`
     (named sizes, upstream config names or a YAML path, model/build.py) with `ckpt_path`
     weights (deterministic synthetic weights when absent, as everywhere offline), as a
@@ -770,7 +818,9 @@ def build_sam2_video_predictor(config_file, ckpt_path=None, device="cuda", mode=
     configs and builder do: three candidate masks on a single click and on tracked frames (the one of
     highest predicted IoU wins and its token is the object pointer), the stability fallback on box /
     multi-click prompts.  The default keeps the single-mask heads of the training configuration.
-    `postprocess_on_device=False` runs the hole filling on the host (scipy) instead of the HIP kernels."""
+    `postprocess_on_device=False` runs the hole filling on the host (scipy) instead of the HIP kernels.
+    `preprocess_on_device=True` resizes and normalises the video's frames on the device (init_state uploads
+    uint8 frames; the same values as the host's PIL path)."""
     from .model.sam2model import SAM2Model, merge_model_overrides
     if multimask:
         kwargs["model_overrides"] = merge_model_overrides(UPSTREAM_MULTIMASK_OVERRIDES,
@@ -781,4 +831,5 @@ def build_sam2_video_predictor(config_file, ckpt_path=None, device="cuda", mode=
     if mode == "eval":
         model.eval()
     return SAM2VideoPredictor(model, fill_hole_area=8 if apply_postprocessing else 0,
-                              binarize_mask_from_pts_for_mem_enc=True, postprocess_on_device=postprocess_on_device)
+                              binarize_mask_from_pts_for_mem_enc=True, postprocess_on_device=postprocess_on_device,
+                              preprocess_on_device=preprocess_on_device)

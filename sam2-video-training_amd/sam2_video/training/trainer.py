@@ -626,6 +626,13 @@ def _static_batch(batch, device):
     return out
 
 
+def _to_device(batch, device):
+    """a loader's batch on the device: copied, or, for the raw clips of `preprocess_on_device`, built there by
+    the preprocessing kernels (data/preprocess.py) -- an ordinary device batch either way"""
+    from ..data.preprocess import to_device_batch
+    return to_device_batch(batch, device, non_blocking=True)
+
+
 # ------------------------------------------------------------------ data module
 class SAM2LightningDataModule(_DataBase):
     """trainer.py:325-400: B == 1 clip DataLoaders collated by sam2_collate_fn.  The data section
@@ -673,6 +680,10 @@ class SAM2LightningDataModule(_DataBase):
         from ..data.synthetic import sam2_collate_fn
         if ds is None:
             raise RuntimeError("dataset not initialized: call setup('fit') first")
+        collate = sam2_collate_fn
+        if getattr(getattr(getattr(ds, "video_dataset", None), "image_dataset", None), "preprocess_on_device", False):
+            # COCO clips with `preprocess_on_device`: uint8 frames + RLE runs, finished on the device
+            from ..data.preprocess import sam2_raw_collate_fn as collate
         sampler = None
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             sampler = DistributedSampler(ds, num_replicas=dist.get_world_size(), rank=dist.get_rank(),
@@ -680,7 +691,7 @@ class SAM2LightningDataModule(_DataBase):
         return DataLoader(ds, batch_size=int(_get(self.data, "batch_size", 1)),
                           num_workers=int(_get(self.data, "num_workers", 0)),
                           shuffle=shuffle if sampler is None else False, sampler=sampler,
-                          pin_memory=torch.cuda.is_available(), collate_fn=sam2_collate_fn)
+                          pin_memory=torch.cuda.is_available(), collate_fn=collate)
 
     def train_dataloader(self):
         return self._loader(self.train_dataset, self.train_shuffle)
@@ -737,7 +748,7 @@ class Trainer:
         for i, batch in enumerate(loader):
             if i >= n:
                 break
-            module.validation_step(batch.to(device, non_blocking=True), i)
+            module.validation_step(_to_device(batch, device), i)
             vals.append({k: float(v) for k, v in module.logged.items() if k.startswith("val/")})
         if vals:
             row = {k: sum(v[k] for v in vals) / len(vals) for k in vals[0]}
@@ -783,7 +794,7 @@ class Trainer:
                 if i >= n_train:
                     break
                 before = run.global_step
-                run(batch.to(device, non_blocking=True))
+                run(_to_device(batch, device))
                 self.global_step = run.global_step
                 if run.global_step != before and run.global_step % self.log_every_n_steps == 0:
                     row = {k: float(v) for k, v in module.logged.items() if k.startswith("train/")}
@@ -825,7 +836,7 @@ def fit(module: SAM2LightningModule, batches, max_steps: int, device="cuda", log
     for i, batch in enumerate(batches):
         if i >= max_steps:
             break
-        run(batch.to(device, non_blocking=True))
+        run(_to_device(batch, device))
         if (i + 1) % log_every == 0:
             row = {k: float(v) for k, v in module.logged.items()}
             row["step"] = i + 1
