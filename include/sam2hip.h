@@ -827,12 +827,17 @@ int s2h_point_embed_bwd_rows(int dt, int R, int D, const int* labels, const void
 int s2h_mask_stats(int N, int64_t P, const float* x, int64_t ldx, const uint8_t* tgt, int64_t ldt,
                    float inv_temp, float* stats, hipStream_t st);
 /* losses[4] = (loss_mask, loss_dice, loss_iou, weighted total) with per-frame
- * normalisation by valid categories (valid = NULL: target sum > 0); coef[3*N] are the
- * gradient coefficients consumed by s2h_mask_loss_bwd. */
+ * normalisation by valid categories (valid = NULL: target sum > 0); losses is added to.
+ * coef[4*N] are the gradient coefficients consumed by s2h_mask_loss_bwd, four per row:
+ * [0] the focal coefficient gscale w_mask / (nv P), [1] Dice A = gscale w_dice 2 / (nv den),
+ * [2] Dice B = gscale w_dice (2 sum(sigma t) + 1) / (nv den^2) with den = sum sigma + sum t + 1,
+ * [3] d total / d pred_iou = gscale w_iou sign(pred_iou - actual) / nv; zeros on an invalid row.
+ * A frame with no valid row leaves losses unchanged and writes an all-zero coef. */
 int s2h_mask_loss_finalize(int N, int64_t P, const float* stats, const float* pred_iou, const int* valid,
                            float w_mask, float w_dice, float w_iou, float gscale, float* losses,
                            float* coef, hipStream_t st);
-/* dx = d(total)/d(logits) * gtot[3] (device scalar upstream gradient); dious likewise. */
+/* dx = d(total)/d(logits) * gtot[3] (device scalar upstream gradient, NULL = 1); dious likewise
+ * (may be NULL).  tgt is required: NULL is refused with hipErrorInvalidValue before any launch. */
 int s2h_mask_loss_bwd(int N, int64_t P, const float* x, int64_t ldx, const uint8_t* tgt, int64_t ldt,
                       float inv_temp, const float* coef, float* dx, int64_t lddx, const float* gtot,
                       float* dious, hipStream_t st);

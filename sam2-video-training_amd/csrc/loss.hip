@@ -251,8 +251,9 @@ extern "C" int s2h_mask_loss_bwd(int N, int64_t P, const float* x, int64_t ldx, 
                                  float* dious, hipStream_t st) {
   const int64_t n = (int64_t)N * P;
   if (n <= 0) return 0;
-  if (N > 256) return (int)hipErrorInvalidValue;
-  if (tgt != nullptr && mask_vec4_ok(P, x, ldx, tgt, ldt) && lddx % 4 == 0 && ((uintptr_t)dx & 15) == 0) {
+  // both kernels read the targets of every row with a non-zero coefficient
+  if (N > 256 || tgt == nullptr) return (int)hipErrorInvalidValue;
+  if (mask_vec4_ok(P, x, ldx, tgt, ldt) && lddx % 4 == 0 && ((uintptr_t)dx & 15) == 0) {
     int64_t b = (n / 4 + 255) / 256;
     if (b > 8192) b = 8192;
     hipLaunchKernelGGL(mask_loss_bwd_vec_kernel, dim3((unsigned)b), dim3(256), 0, st, N, P, x, ldx, tgt, ldt, inv_temp,
