@@ -673,6 +673,17 @@ int s2h_cc_label_u8(int N, int H, int W, const uint8_t* mask, int positive, int*
  * number of its runs when there is none).  A zero-length first run (the mask starts set) and a single run (an
  * empty mask) are valid; run_off [A + 1] ascending from 0. */
 int s2h_rle_decode(int A, int H, int W, const int* run_off, const int* run_end, uint8_t* mask, hipStream_t st);
+/* Offline scoring from the runs (reference sam2_video/eval/eval.py:88-103; csrc/pair_counts.h): group g is one
+ * (image, category) pair of H x W images; its predicted annotations are [dt_grp_off[g], dt_grp_off[g + 1]) of
+ * dt_run_off / dt_run_end, its ground-truth ones [gt_grp_off[g], gt_grp_off[g + 1]) of gt_run_off / gt_run_end
+ * (both in the s2h_rle_decode layout; *_grp_off [G + 1] ascending from 0).  counts[4 g ..] = |p & g|, |p | g|,
+ * |p|, |g| as uint64 (zeroed by the call), p and g the OR of the side's annotations; an empty side is an empty
+ * mask.  No dense mask is written anywhere; both sides are column-major positions, nothing is transposed.
+ * Integer arithmetic and integer atomics only; at most 4096 annotations per group and side are read.  Limits of
+ * s2h_rle_decode with G in place of A. */
+int s2h_rle_pair_counts(int G, int H, int W, const int* dt_grp_off, const int* dt_run_off, const int* dt_run_end,
+                        const int* gt_grp_off, const int* gt_run_off, const int* gt_run_end, uint64_t* counts,
+                        hipStream_t st);
 /* Rectangular dilation (op 0) or erosion (op 1) of byte masks [N, H, W] (nonzero = set; out is 0 / 1):
  * out(y, x) = OR resp. AND of in(y + dy, x + dx) over dy in [y_lo, y_hi], dx in [x_lo, x_hi], restricted to the
  * positions inside the image -- outside pixels are ignored by both, cv2's default morphology border.
@@ -886,6 +897,14 @@ int s2h_grad_norm(int64_t n, const float* g, float* partial_ws, float max_norm, 
  * p -= lr/(1-b1^step) * m / (sqrt(v)/sqrt(1-b2^step) + eps); optional bf16 shadow copy. */
 int s2h_adamw(int64_t n, float* p, const float* g, float* m, float* v, const float* clip, float lr,
               float beta1, float beta2, float eps, float wd, int step, void* bf16_shadow, hipStream_t st);
+/* Stochastic weight averaging over the flat master arena (Lightning's StochasticWeightAveraging.avg_fn with its
+ * device-tensor divisor).  s2h_swa_update: n_averaged == 0 copies p into avg; otherwise
+ * avg = avg + (p - avg) / (float)(n_averaged + 1) in fp32 -- a subtraction, a correctly rounded IEEE division (no
+ * reciprocal) and an addition, each rounded once.  s2h_swa_apply: p = avg and, when bf16_shadow is not NULL, the
+ * shadow in the rounding of s2h_adamw / s2h_cast.  Both write in place (captured graphs that read p or the
+ * shadow stay valid); n elements, 16-B accesses when the pointers are 16-B (shadow: 8-B) aligned. */
+int s2h_swa_update(int64_t n, float* avg, const float* p, int n_averaged, hipStream_t st);
+int s2h_swa_apply(int64_t n, const float* avg, float* p, void* bf16_shadow, hipStream_t st);
 
 /* ---------------------------------------------------------------- prompt stage (host CPU code)
  * The per-step host work of prepare_prompt_inputs (sam2model.py:181-236) on frame 0, native and

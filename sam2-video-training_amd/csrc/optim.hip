@@ -146,3 +146,87 @@ extern "C" int s2h_adamw(int64_t n, float* p, const float* g, float* m, float* v
   }
   return (int)hipGetLastError();
 }
+
+// ------------------------------------------------------------------ stochastic weight averaging
+// The running average of the master arena (Lightning's StochasticWeightAveraging.avg_fn with its device-tensor
+// divisor): avg += (p - avg) / (n_averaged + 1), three separately rounded fp32 operations -- a subtraction, an
+// IEEE division (no reciprocal) and an addition; there is no product, so nothing contracts into an fma.
+// n_averaged == 0 copies.  Grid-stride, 16-B accesses on the aligned body, the scalar kernel on the tail.
+__device__ __forceinline__ float swa_elem(float a, float p, float div) { return a + __fdiv_rn(p - a, div); }
+__global__ __launch_bounds__(256) void swa_update_kernel(int64_t n, float* avg, const float* p, float div, int copy) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    avg[i] = copy ? p[i] : swa_elem(avg[i], p[i], div);
+}
+__global__ __launch_bounds__(256) void swa_update_vec_kernel(int64_t n4, float4* avg, const float4* p, float div,
+                                                             int copy) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const float4 q = p[i];
+    if (copy) {
+      avg[i] = q;
+    } else {
+      const float4 a = avg[i];
+      avg[i] = float4{swa_elem(a.x, q.x, div), swa_elem(a.y, q.y, div), swa_elem(a.z, q.z, div),
+                      swa_elem(a.w, q.w, div)};
+    }
+  }
+}
+extern "C" int s2h_swa_update(int64_t n, float* avg, const float* p, int n_averaged, hipStream_t st) {
+  if (n <= 0) return 0;
+  if (!avg || !p || n_averaged < 0) return (int)hipErrorInvalidValue;
+  const float div = (float)(n_averaged + 1);
+  const int copy = n_averaged == 0;
+  const bool vec = (((uintptr_t)avg | (uintptr_t)p) & 15) == 0;
+  const int64_t n4 = vec ? n / 4 : 0;
+  if (n4 > 0) {
+    int64_t b = (n4 + 255) / 256;
+    if (b > 8192) b = 8192;
+    hipLaunchKernelGGL(swa_update_vec_kernel, dim3((unsigned)b), dim3(256), 0, st, n4, (float4*)avg, (const float4*)p,
+                       div, copy);
+  }
+  const int64_t done = 4 * n4, rest = n - done;  // the tail (or everything when unaligned)
+  if (rest > 0) {
+    int64_t b = (rest + 255) / 256;
+    if (b > 4096) b = 4096;
+    hipLaunchKernelGGL(swa_update_kernel, dim3((unsigned)b), dim3(256), 0, st, rest, avg + done, p + done, div, copy);
+  }
+  return (int)hipGetLastError();
+}
+
+// p = avg, and the bf16 shadow in the rounding of s2h_adamw / s2h_cast (the (bf16) conversion)
+__global__ __launch_bounds__(256) void swa_apply_kernel(int64_t n, const float* avg, float* p, bf16* shadow) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float a = avg[i];
+    p[i] = a;
+    if (shadow) shadow[i] = (bf16)a;
+  }
+}
+__global__ __launch_bounds__(256) void swa_apply_vec_kernel(int64_t n4, const float4* avg, float4* p, uint2* shadow) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const float4 a = avg[i];
+    p[i] = a;
+    if (shadow) {
+      bf16 t4[4] = {(bf16)a.x, (bf16)a.y, (bf16)a.z, (bf16)a.w};
+      shadow[i] = *(const uint2*)t4;
+    }
+  }
+}
+extern "C" int s2h_swa_apply(int64_t n, const float* avg, float* p, void* bf16_shadow, hipStream_t st) {
+  if (n <= 0) return 0;
+  if (!avg || !p) return (int)hipErrorInvalidValue;
+  const bool vec = (((uintptr_t)avg | (uintptr_t)p) & 15) == 0 && ((uintptr_t)bf16_shadow & 7) == 0;
+  const int64_t n4 = vec ? n / 4 : 0;
+  if (n4 > 0) {
+    int64_t b = (n4 + 255) / 256;
+    if (b > 8192) b = 8192;
+    hipLaunchKernelGGL(swa_apply_vec_kernel, dim3((unsigned)b), dim3(256), 0, st, n4, (const float4*)avg, (float4*)p,
+                       (uint2*)bf16_shadow);
+  }
+  const int64_t done = 4 * n4, rest = n - done;
+  if (rest > 0) {
+    int64_t b = (rest + 255) / 256;
+    if (b > 4096) b = 4096;
+    hipLaunchKernelGGL(swa_apply_kernel, dim3((unsigned)b), dim3(256), 0, st, rest, avg + done, p + done,
+                       bf16_shadow ? (bf16*)bf16_shadow + done : (bf16*)nullptr);
+  }
+  return (int)hipGetLastError();
+}

@@ -24,8 +24,13 @@
 //      statistics per category in workgroup order -> the header;
 //   3. every workgroup scans its 256 counts again and writes its positions behind its offset.
 //   Integer arithmetic in a fixed order throughout: the output is a pure function of the bits.
+// s2h_rle_pair_counts: the offline scoring's four counts per (image, category) group from the run boundaries
+//   of its predicted and ground-truth annotations (pair_counts.h): a wave is one word of 64 column-major
+//   positions, a lane searches its position in every annotation of a side, the two ballots are the words of
+//   the OR-ed masks.  No mask is stored.  Integer adds (uint64 atomics, one per workgroup and count).
 #include "bilinear_tap.h"
 #include "common.h"
+#include "pair_counts.h"
 #include "reduce_det.h"
 #include "rle_scan.h"
 #include "sweep_hist.h"
@@ -324,6 +329,38 @@ __global__ __launch_bounds__(RLE_BLOCK_WORDS) void rle_emit_kernel(int nbw, int 
   rle_emit(r.t, r.base, trans, off[f] + e, cap);
 }
 
+
+// counts[g] += the counts of the PC_BLOCK / 64 words of workgroup b of group g (blockIdx.x = g * nbw + b);
+// counts is zero on entry.  A group with no annotation on either side reads nothing.
+__global__ __launch_bounds__(PC_BLOCK) void rle_pair_counts_kernel(int nbw, int HW, const int* dt_grp_off,
+                                                                  const int* dt_run_off, const int* dt_run_end,
+                                                                  const int* gt_grp_off, const int* gt_run_off,
+                                                                  const int* gt_run_end, unsigned long long* counts) {
+  __shared__ int red[PC_BLOCK / 64][4];
+  const int g = blockIdx.x / nbw, b = blockIdx.x - g * nbw;
+  const int d0 = dt_grp_off[g], d1 = dt_grp_off[g + 1], g0 = gt_grp_off[g], g1 = gt_grp_off[g + 1];
+  if (d1 <= d0 && g1 <= g0) return;  // (the same for every thread of the workgroup)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int pos = (b * (PC_BLOCK / 64) + wave) * 64 + lane;  // (the host checked G H W + 256 < 2^31)
+  const bool in = pos < HW;
+  const uint64_t p = __ballot(in && pc_side_bit(dt_run_off, dt_run_end, d0, d1, pos));
+  const uint64_t q = __ballot(in && pc_side_bit(gt_run_off, gt_run_end, g0, g1, pos));
+  if (lane == 0) {
+    const PcCounts c = pc_word_counts(p, q);
+    red[wave][0] = c.inter;
+    red[wave][1] = c.uni;
+    red[wave][2] = c.np;
+    red[wave][3] = c.ng;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    int v = 0;
+#pragma unroll
+    for (int w = 0; w < PC_BLOCK / 64; ++w) v += red[w][threadIdx.x];
+    if (v) atomicAdd(&counts[(int64_t)g * 4 + threadIdx.x], (unsigned long long)v);
+  }
+}
+
 // ceil(H W / 64), or -1 when the sizes are outside what the kernels index (those of s2h_cc_label)
 int rle_words(int Ncat, int H, int W) {
   if (Ncat < 0 || H < 1 || W < 1 || (int64_t)H * W > RLE_MAX_PIXELS) return -1;
@@ -398,5 +435,20 @@ extern "C" int s2h_rle_transitions(int Ncat, int H, int W, const uint64_t* bits,
                      off, hdr);
   hipLaunchKernelGGL(rle_emit_kernel, dim3((unsigned)F), dim3(RLE_BLOCK_WORDS), 0, st, nbw, nw, H * W, bits,
                      (const int*)off, capacity, trans);
+  S2H_LAUNCH_CHECK();
+}
+
+extern "C" int s2h_rle_pair_counts(int G, int H, int W, const int* dt_grp_off, const int* dt_run_off,
+                                   const int* dt_run_end, const int* gt_grp_off, const int* gt_run_off,
+                                   const int* gt_run_end, uint64_t* counts, hipStream_t st) {
+  const int nw = rle_words(G, H, W);  // the limits of s2h_rle_decode, G in place of A
+  if (nw < 0) return (int)hipErrorInvalidValue;
+  if (G == 0) return 0;
+  // (run_end of a side may be NULL when that side has no annotation at all: it is never read then)
+  if (!dt_grp_off || !dt_run_off || !gt_grp_off || !gt_run_off || !counts) return (int)hipErrorInvalidValue;
+  s2h_zero_f32((float*)counts, 1, (int64_t)G * 8, (int64_t)G * 8, st);  // (uint64 0 = two 0.0f bit patterns)
+  const int nbw = (nw + PC_BLOCK / 64 - 1) / (PC_BLOCK / 64);  // (G * nbw <= G H W / 256 + G < 2^31)
+  hipLaunchKernelGGL(rle_pair_counts_kernel, dim3((unsigned)(G * nbw)), dim3(PC_BLOCK), 0, st, nbw, H * W, dt_grp_off,
+                     dt_run_off, dt_run_end, gt_grp_off, gt_run_off, gt_run_end, (unsigned long long*)counts);
   S2H_LAUNCH_CHECK();
 }

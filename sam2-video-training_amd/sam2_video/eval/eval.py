@@ -128,7 +128,39 @@ def _merged_counts(anns_dt, anns_gt):
     return [int((p & g).sum()), int((p | g).sum()), int(p.sum()), int(g.sum())], p.size
 
 
-def eval(predict_path, coco_path, output_path, remove_background=False):  # noqa: A001 (the reference's name)
+def _device_counts(images, by_image, cat_ids, device="cuda"):
+    """{(image id, category id): (the four counts, pixel count)} for every (image, category) group with an
+    annotation on either side, counted on the device from the run boundaries (ops.rle_pair_counts:
+    s2h_rle_pair_counts) -- the groups batched by mask size, one launch per size (split where a batch would pass
+    the kernel's G H W < 2^31 limit); nothing is decoded on the host and only the runs are uploaded"""
+    from ..data import rle
+    batches: Dict = {}
+    for img in images:
+        anns_dt, anns_gt = by_image["dt"].get(img["id"], []), by_image["gt"].get(img["id"], [])
+        for c in cat_ids:
+            sides = [[rle.counts_of(a["segmentation"]) for a in anns if a["category_id"] == c]
+                     for anns in (anns_dt, anns_gt)]
+            if not sides[0] and not sides[1]:
+                continue
+            shapes = {(h, w) for side in sides for h, w, _ in side}
+            if len(shapes) != 1:
+                raise ValueError(f"image {img['id']}, category {c}: annotation masks of sizes {sorted(shapes)}")
+            keys, dts, gts = batches.setdefault(shapes.pop(), ([], [], []))
+            keys.append((img["id"], c))
+            dts.append([cnts for _, _, cnts in sides[0]])
+            gts.append([cnts for _, _, cnts in sides[1]])
+    out = {}
+    for (h, w), (keys, dts, gts) in batches.items():
+        step = max(1, (2 ** 31 - 257) // (h * w))
+        for i in range(0, len(keys), step):
+            counts = ops.rle_pair_counts(dts[i:i + step], gts[i:i + step], h, w, device=device).cpu().numpy()
+            for key, row in zip(keys[i:i + step], counts):
+                out[key] = ([int(v) for v in row], h * w)
+    return out
+
+
+def eval(predict_path, coco_path, output_path, remove_background=False, *,  # noqa: A001 (the reference's name)
+         score_on_device=None):
     """eval.py:53-277 without pycocotools: score `predict_path` (the annotation list inference() writes) against
     the ground-truth COCO file and write `<output_path>/eval.pkl` -- {"videos": [{"video_id", "frames": [{"video_id",
     "order_in_video", "cat_scores", "avg_scores"}], "cat_scores", "avg_scores"}], "cat_scores", "avg_scores"} with
@@ -139,7 +171,12 @@ def eval(predict_path, coco_path, output_path, remove_background=False):  # noqa
     the nanmeans); the four counts go through image_scores_from_counts, whose closed forms are caculate_iou /
     caculate_dice / caculate_mae on the uint8 masks.  (One corner differs: annotations that exist on both sides
     but are all empty score NaN here and 0 in the reference; neither inference() nor a COCO export writes empty
-    masks.)  Videos are listed in first-seen order (the reference iterates a set).  Host numpy throughout."""
+    masks.)  Videos are listed in first-seen order (the reference iterates a set).
+
+    score_on_device (None: True when torch.cuda.is_available()): the four counts of every (image, category) group
+    come from s2h_rle_pair_counts, straight from the run boundaries (_device_counts), instead of the host's
+    decode / OR / sum; the same integers go through the same image_scores_from_counts, so eval.pkl is identical.
+    False: host numpy throughout."""
     import json
     import os
     import pickle
@@ -156,6 +193,12 @@ def eval(predict_path, coco_path, output_path, remove_background=False):  # noqa
     for side, anns in (("dt", predictions), ("gt", gt.get("annotations", []))):
         for a in anns:
             by_image[side].setdefault(a["image_id"], []).append(a)
+    if score_on_device is None:
+        score_on_device = torch.cuda.is_available()
+    on_device = None
+    if score_on_device:
+        on_device = _device_counts([i for i in gt.get("images", []) if i.get("is_det_keyframe") is not False],
+                                   by_image, cat_ids)
     img_scores: List[Dict] = []
     for img in gt.get("images", []):
         if img.get("is_det_keyframe") is False:
@@ -168,7 +211,7 @@ def eval(predict_path, coco_path, output_path, remove_background=False):  # noqa
             if not c_dt and not c_gt:
                 counts.append([0, 0, 0, 0])
                 continue
-            row, num_pixels = _merged_counts(c_dt, c_gt)
+            row, num_pixels = on_device[(img["id"], c)] if on_device is not None else _merged_counts(c_dt, c_gt)
             counts.append(row)
         score = {"video_id": img["video_id"], "order_in_video": img["order_in_video"]}
         score.update(image_scores_from_counts(np.asarray(counts, dtype=np.int64).reshape(-1, 4), max(num_pixels, 1),

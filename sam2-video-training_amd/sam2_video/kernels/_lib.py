@@ -135,6 +135,7 @@ SIGNATURES = {
     "s2h_fill_holes": [I, I, I, P, I, P, P, P],
     "s2h_cc_label_u8": [I, I, I, P, I, P, P, P],
     "s2h_rle_decode": [I, I, I, P, P, P, P],
+    "s2h_rle_pair_counts": [I, I, I, P, P, P, P, P, P, P, P],
     "s2h_morph_rect": [I, I, I, P, I, I, I, I, I, P, P, P],
     "s2h_cc_components": [I, I, I, P, P, I, P, I, P, P, P, P, P],
     "s2h_mask_rank_select": [I, P, P, P, P, I, I, I, P, P, P, P, P, P],
@@ -162,6 +163,8 @@ SIGNATURES = {
     "s2h_sigmoid_grad_axpy": [I, L, P, L, P, P, L, P],
     "s2h_grad_norm": [L, P, P, F, F, P, P],
     "s2h_adamw": [L, P, P, P, P, P, F, F, F, F, F, I, P, P],
+    "s2h_swa_update": [L, P, P, I, P],
+    "s2h_swa_apply": [L, P, P, P, P],
     "s2h_pos_embed": [I, I, I, I, I, P, P, P, P],
     "s2h_pos_embed_bwd": [I, I, I, I, I, P, P, P, P],
     "s2h_point_embed": [I, I, I, P, P, P, P, P, P],

@@ -109,6 +109,7 @@ class ParamArena:
         self.exp_avg_sq = torch.zeros_like(self.grad)
         self.shadow = (torch.zeros(self.total, dtype=torch.bfloat16, device=device)
                        if compute_dtype == torch.bfloat16 else None)
+        self.swa = None  # running average of `data` (swa_buffer)
         self.params = params
         for n in order:
             p = params[n]
@@ -151,6 +152,27 @@ class ParamArena:
     def refresh_shadow(self):
         if self.shadow is not None:
             ops.cast(self.data, torch.bfloat16, out=self.shadow)
+
+    # ---- stochastic weight averaging (training/callbacks.py StochasticWeightAveraging)
+    def swa_buffer(self):
+        """the fp32 running average of the whole master arena, allocated at the first call (only runs
+        that average pay for it).  Call it before a step graph is captured -- the callback does, in
+        on_fit_start: an allocation inside a capture would land in the graph's private pool."""
+        if self.swa is None:
+            if self.data.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ParamArena.swa_buffer: first call inside a graph capture")
+            self.swa = torch.zeros_like(self.data)
+        return self.swa
+
+    def swa_update(self, n_averaged: int):
+        """swa = data (n_averaged == 0) or swa + (data - swa) / (n_averaged + 1) over the whole arena:
+        frozen parameters average to themselves, the optimizer moments are not touched"""
+        ops.swa_update(self.swa_buffer(), self.data, n_averaged)
+
+    def swa_apply(self):
+        """data = swa and the bf16 shadow recast, both written in place: every parameter view and every
+        captured step graph keeps pointing at valid, now averaged, weights"""
+        ops.swa_apply(self.swa_buffer(), self.data, self.shadow)
 
     def zero_grad(self):
         self.grad.zero_()

@@ -1400,6 +1400,39 @@ def rle_decode(counts_list, H, W, device="cuda"):
     return mask
 
 
+PC_MAX_GROUP_ANNS = 1 << 12  # csrc/pair_counts.h: annotations per group and side
+
+
+def rle_pair_counts(dt_groups, gt_groups, H, W, device="cuda"):
+    """Offline scoring counts from the runs (s2h_rle_pair_counts).  dt_groups / gt_groups: G lists, one per
+    (image, category) group of H x W images, of COCO counts (one list of run lengths per annotation) of the
+    predicted resp. ground-truth side.  -> int64 [G, 4] on the device: |p & g|, |p | g|, |p|, |g| of the OR-ed
+    sides.  Only the run boundaries are uploaded (rle_runs); no mask is decoded."""
+    G = len(dt_groups)
+    if len(gt_groups) != G:
+        raise ValueError(f"{G} predicted groups, {len(gt_groups)} ground-truth groups")
+    bufs = []
+    for side, groups in (("predicted", dt_groups), ("ground-truth", gt_groups)):
+        sizes = [len(g) for g in groups]
+        if sizes and max(sizes) > PC_MAX_GROUP_ANNS:
+            raise ValueError(f"a group has {max(sizes)} {side} annotations; at most {PC_MAX_GROUP_ANNS} are read")
+        grp_off = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int32)
+        run_off, run_end = rle_runs([c for g in groups for c in g], H, W)
+        if run_end.size == 0:
+            run_end = np.zeros(1, np.int32)  # never read: no annotation on this side
+        bufs += [grp_off, run_off, run_end]
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("libsam2hip kernels run on the GPU only (device %s)" % dev)
+    out = torch.empty(G, 4, device=dev, dtype=torch.int64)
+    if G == 0:
+        return out
+    with torch.cuda.device(out.device):
+        d = [torch.from_numpy(b).to(out.device) for b in bufs]
+        call("s2h_rle_pair_counts", G, int(H), int(W), *[ptr(t) for t in d], ptr(out), stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------- clip loading
 RS_BITS = 22       # csrc/resample_u8.h: Pillow's PRECISION_BITS
 RS_MAX_TAPS = 64   # taps per output sample
@@ -1904,6 +1937,26 @@ def grad_norm(g, max_norm, ws, out, grad_scale=1.0):
 def adamw(p, g, m, v, clip, lr, beta1, beta2, eps, wd, step, shadow=None):
     call("s2h_adamw", p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), ptr(clip), float(lr), float(beta1), float(beta2),
          float(eps), float(wd), int(step), ptr(shadow), stream())
+
+
+def swa_update(avg, p, n_averaged):
+    """avg = p (n_averaged == 0) or avg + (p - avg) / (n_averaged + 1), in place (s2h_swa_update): fp32, an
+    IEEE division -- Lightning's StochasticWeightAveraging.avg_fn with its device-tensor divisor"""
+    _dev(avg, p)
+    assert avg.dtype == p.dtype == torch.float32 and avg.numel() == p.numel()
+    assert avg.is_contiguous() and p.is_contiguous() and int(n_averaged) >= 0
+    call("s2h_swa_update", avg.numel(), ptr(avg), ptr(p), int(n_averaged), stream())
+    return avg
+
+
+def swa_apply(avg, p, shadow=None):
+    """p = avg and shadow = bf16(avg) (the rounding of adamw / cast), written in place (s2h_swa_apply)"""
+    _dev(avg, p, shadow)
+    assert avg.dtype == p.dtype == torch.float32 and avg.numel() == p.numel()
+    assert avg.is_contiguous() and p.is_contiguous()
+    assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.numel() == p.numel() and shadow.is_contiguous())
+    call("s2h_swa_apply", p.numel(), ptr(avg), ptr(p), ptr(shadow), stream())
+    return p
 
 
 def pos_embed(Y, win, h, w, out):

@@ -39,6 +39,11 @@ _LIGHTNING = {
     "lightning.pytorch.Trainer": "sam2_video.training.trainer.Trainer",
     "lightning.Trainer": "sam2_video.training.trainer.Trainer",
 }
+# ... and the callbacks of the configs' `callbacks` lists (best.yaml:115-135, dice_main.yaml) to
+# training/callbacks.py, which this build's Trainer drives; with Lightning installed its own classes run
+_LIGHTNING.update({f"lightning.pytorch.callbacks.{_n}": f"sam2_video.training.callbacks.{_n}"
+                   for _n in ("ModelCheckpoint", "EarlyStopping", "StochasticWeightAveraging",
+                              "LearningRateMonitor", "ModelSummary")})
 
 
 def _resolve(target: str):

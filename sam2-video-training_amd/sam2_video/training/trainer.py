@@ -14,10 +14,15 @@ sam2_video/training/trainer.py:28-400) and a Lightning-API Trainer for them.
 * `Trainer(**cfg.trainer)`: the `lightning.pytorch.Trainer` arguments the
   reference configs set (best.yaml:98-113) -- max_epochs / max_steps,
   accumulate_grad_batches, gradient_clip_val (0 / None = no clip, as Lightning),
-  precision, val_check_interval, num_sanity_val_steps, limit_*_batches -- and
-  `fit(module, datamodule)`.  `model/build.py` resolves the configs'
-  `_target_: lightning.pytorch.trainer.trainer.Trainer` to it when Lightning is
-  not installed (it is not in this image).
+  precision, val_check_interval, num_sanity_val_steps, limit_*_batches,
+  callbacks, default_root_dir -- and `fit(module, datamodule)`.  `model/build.py`
+  resolves the configs' `_target_: lightning.pytorch.trainer.trainer.Trainer` to
+  it when Lightning is not installed (it is not in this image).  `callbacks`
+  (training/callbacks.py: ModelCheckpoint, EarlyStopping,
+  StochasticWeightAveraging, ...) get on_fit_start, on_train_epoch_start,
+  on_validation_end (after every validation but the sanity one),
+  on_train_epoch_end and on_train_end; `callback_metrics`, `should_stop`,
+  `checkpoint_callback` and `early_stopping_callback` are Lightning's attributes.
 * `StepRunner`: one micro-step of the fit loop on the device (captured HIP
   graph per input signature), RCCL all-reduce + clip + AdamW at accumulation
   boundaries.
@@ -28,6 +33,7 @@ W&B GIF logging is out of scope.
 """
 from __future__ import annotations
 
+import gc
 import math
 import os
 import time
@@ -406,6 +412,9 @@ class StepRunner:
         self.accumulate = max(1, int(accumulate_grad_batches or 1))
         self.global_step = 0  # optimizer steps
         self.micro_step = 0
+        # a learning rate that replaces the schedule's until it is set back to None (the SWA phase:
+        # Trainer.set_epoch_lr, training/callbacks.py StochasticWeightAveraging)
+        self.lr_override: Optional[float] = None
         self.graph = graph
         self._graphs: Dict[Any, Dict[str, Any]] = {}
         self.before_capture = None  # optional callable, run right before a graph is captured
@@ -496,6 +505,12 @@ class StepRunner:
                 model.arena.zero_grad()
             if self.before_capture is not None:
                 self.before_capture()
+            # A dead Python cycle can hold an earlier fit's captured graphs and their private pool (trainer
+            # <-> module <-> runner: Trainer.fit sets module.trainer_).  Collected while this capture is
+            # open, its graphs and pool would be destroyed inside the capture -- the process has aborted in
+            # exactly that state ("Garbage-collecting" under the capture below, no message).  torch.cuda.graph
+            # no longer collects on entry (torch >= 2.9: only with force_cudagraph_gc), so collect here.
+            gc.collect()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 loss = self._device_step(static)
@@ -549,11 +564,24 @@ class StepRunner:
             if not reduced:
                 self.reducer.reduce()
             scale *= self.reducer.grad_scale
-        lr = m.lr_at(self.global_step) if m.lr_at is not None else None
+        lr = self.next_lr()
         m.optimizer.step(lr=lr, grad_scale=scale)
         m.log("train/learning_rate", m.optimizer.param_groups[0]["lr"])
         self.global_step += 1
         return True
+
+    def next_lr(self) -> Optional[float]:
+        """the rate the next optimizer step is given: the override, else the schedule's (None: the optimizer
+        keeps the rate it holds)"""
+        if self.lr_override is not None:
+            return self.lr_override
+        m = self.module
+        return m.lr_at(self.global_step) if m.lr_at is not None else None
+
+    def discard_window(self):
+        """drop an open, partial accumulation window without stepping (the fit loop leaves on should_stop):
+        the next micro-step starts a new window and zeroes the arena"""
+        self.micro_step -= self.micro_step % self.accumulate
 
     def __call__(self, batch):
         self.begin_micro_step()
@@ -703,13 +731,17 @@ class SAM2LightningDataModule(_DataBase):
 # ---------------------------------------------------------------------- trainer
 class Trainer:
     """The `lightning.pytorch.Trainer` surface the reference configs use (best.yaml:98-113), driving
-    SAM2LightningModule through StepRunner.  Unknown Lightning arguments (logger, callbacks,
-    enable_progress_bar, ...) are accepted and ignored."""
+    SAM2LightningModule through StepRunner.  `callbacks` are driven as the module docstring says;
+    other unknown Lightning arguments (logger, enable_progress_bar, ...) are accepted and ignored.
+    With more than one rank the validation values in `callback_metrics` are the mean over the ranks
+    (one small all-reduce per validation), so every rank's callbacks see the same monitored value and
+    take the same decision; only rank 0 writes or deletes files."""
 
     def __init__(self, accelerator="auto", devices=1, precision=None, max_epochs=None, max_steps=-1,
                  gradient_clip_val=None, accumulate_grad_batches=1, val_check_interval=1.0,
                  num_sanity_val_steps=0, limit_train_batches=None, limit_val_batches=None,
-                 log_every_n_steps=50, strategy="auto", graph=True, default_root_dir=None, **unused):
+                 log_every_n_steps=50, strategy="auto", graph=True, default_root_dir=None, callbacks=None,
+                 **unused):
         if str(accelerator).lower() == "cpu":
             # the reference's config 1 (overfit.yaml, trainer.accelerator=cpu): this build's step is
             # HIP kernels only -- refuse rather than run on the GPU behind the caller's back
@@ -734,6 +766,54 @@ class Trainer:
         self.val_history: List[Dict[str, float]] = []
         self.global_step = 0
         self.current_epoch = 0
+        if callbacks is None:
+            callbacks = []
+        elif not isinstance(callbacks, (list, tuple)):
+            callbacks = [callbacks]
+        self.callbacks = list(callbacks)
+        self.callback_metrics: Dict[str, float] = {}
+        self.should_stop = False
+        self.module = None
+        self.runner = None
+
+    # ---------------------------------------------------------------- callbacks
+    def _first_callback(self, name):
+        from . import callbacks as C
+        return next((cb for cb in self.callbacks if isinstance(cb, getattr(C, name))), None)
+
+    @property
+    def checkpoint_callback(self):
+        """the first ModelCheckpoint of `callbacks`, or None"""
+        return self._first_callback("ModelCheckpoint")
+
+    @property
+    def early_stopping_callback(self):
+        return self._first_callback("EarlyStopping")
+
+    @property
+    def is_global_zero(self) -> bool:
+        import torch.distributed as dist
+        return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+
+    def _call_hook(self, hook):
+        for cb in self.callbacks:
+            fn = getattr(cb, hook, None)
+            if fn is not None:
+                fn(self, self.module)
+
+    def _train_metrics(self):
+        """the latest logged train/ values into callback_metrics (reads device scalars: called where a
+        callback may look and at epoch ends, not per step)"""
+        self.callback_metrics.update({k: float(v) for k, v in self.module.logged.items() if k.startswith("train/")})
+
+    def current_lr(self) -> float:
+        """the learning rate the next optimizer step will use"""
+        lr = self.runner.next_lr()
+        return float(lr if lr is not None else self.module.optimizer.param_groups[0]["lr"])
+
+    def set_epoch_lr(self, lr: Optional[float]):
+        """fix the learning rate of the following optimizer steps (None: back to the per-step schedule)"""
+        self.runner.lr_override = None if lr is None else float(lr)
 
     @staticmethod
     def _limit(n, lim):
@@ -752,8 +832,23 @@ class Trainer:
             vals.append({k: float(v) for k, v in module.logged.items() if k.startswith("val/")})
         if vals:
             row = {k: sum(v[k] for v in vals) / len(vals) for k in vals[0]}
+            # what callbacks decide on is the mean over the ranks (without callbacks: this rank's values)
+            self.callback_metrics.update(self._mean_over_ranks(row, device) if self.callbacks else row)
             row["step"] = self.global_step
             self.val_history.append(row)
+
+    @staticmethod
+    def _mean_over_ranks(row, device):
+        """with more than one rank: the mean of every value over the ranks, in one all-reduce of len(row) doubles
+        (the ranks log the same keys)"""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return row
+        keys = sorted(row)
+        t = torch.tensor([row[k] for k in keys], dtype=torch.float64, device=device)
+        dist.all_reduce(t)
+        t /= dist.get_world_size()
+        return dict(zip(keys, t.tolist()))
 
     def fit(self, module: SAM2LightningModule, datamodule=None, train_dataloaders=None, val_dataloaders=None):
         from .ddp import init_from_env
@@ -768,6 +863,8 @@ class Trainer:
             train_dataloaders = datamodule.train_dataloader()
             val_dataloaders = datamodule.val_dataloader()
         module.trainer_ = self
+        self.module = module
+        self.should_stop = False
         module.setup("fit", device)
         n_train = self._limit(len(train_dataloaders), self.limit_train_batches)
         n_val = self._limit(len(val_dataloaders), self.limit_val_batches) if val_dataloaders is not None else 0
@@ -778,9 +875,11 @@ class Trainer:
                          accumulate_grad_batches=self.accumulate_grad_batches,
                          gradient_clip_val=self.gradient_clip_val)
         self.runner = run
-        if n_val and self.num_sanity_val_steps:
+        self._call_hook("on_fit_start")
+        if n_val and self.num_sanity_val_steps:  # (the sanity validation triggers no callback)
             self._validate(module, val_dataloaders, device, min(n_val, self.num_sanity_val_steps))
             self.val_history.clear()
+            self.callback_metrics.clear()
         vci = self.val_check_interval
         val_every = (max(1, int(n_train * vci)) if isinstance(vci, float) and vci <= 1.0 else int(vci)) if n_val else 0
         t0 = time.time()
@@ -790,6 +889,7 @@ class Trainer:
             sampler = getattr(train_dataloaders, "sampler", None)
             if hasattr(sampler, "set_epoch"):
                 sampler.set_epoch(epoch)
+            self._call_hook("on_train_epoch_start")
             for i, batch in enumerate(train_dataloaders):
                 if i >= n_train:
                     break
@@ -802,22 +902,34 @@ class Trainer:
                     self.history.append(row)
                 if val_every and (i + 1) % val_every == 0:
                     self._validate(module, val_dataloaders, device, n_val)
+                    if self.callbacks:
+                        self._train_metrics()
+                    self._call_hook("on_validation_end")
+                    if self.should_stop:  # (EarlyStopping) leave right after this validation
+                        run.discard_window()  # an open, partial accumulation window is not stepped
+                        done = True
+                        break
                 if self.max_steps > 0 and run.global_step >= self.max_steps:
                     done = True
                     break
+            if not done and run.flush():  # the epoch's last, partial accumulation window
+                self.global_step = run.global_step
+            self._train_metrics()
+            self._call_hook("on_train_epoch_end")
             if done:
                 break
-            if run.flush():  # the epoch's last, partial accumulation window
-                self.global_step = run.global_step
+        self._call_hook("on_train_end")
         return self.history
 
-    def save_checkpoint(self, path, module: SAM2LightningModule):
+    def save_checkpoint(self, path, module: Optional[SAM2LightningModule] = None):
         """Lightning-layout checkpoint: state_dict with the `model.` prefix (the reference strips it
         when it reloads, train.py:146-157) + optimizer state + counters.  Written by global rank 0
-        only (Lightning's rank-zero checkpointing); the parameters are identical on every rank."""
+        only (Lightning's rank-zero checkpointing); the parameters are identical on every rank.
+        `module` defaults to the one being fitted (Lightning's trainer.save_checkpoint(path))."""
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
             return
+        module = self.module if module is None else module
         sd = {"model." + k: v.detach().cpu() for k, v in module.model.state_dict().items()}
         torch.save({"state_dict": sd, "optimizer_states": [module.optimizer.state_dict()],
                     "global_step": self.global_step, "epoch": self.current_epoch}, path)
