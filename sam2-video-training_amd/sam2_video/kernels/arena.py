@@ -174,6 +174,49 @@ class ParamArena:
         captured step graph keeps pointing at valid, now averaged, weights"""
         ops.swa_apply(self.swa_buffer(), self.data, self.shadow)
 
+    # ---- arena-shaped tensors in files: per parameter name, never flat (the flat layout depends on the
+    # ordering rules above, which may change between builds)
+    def _names(self, which):
+        return self.grad_names if which == "grad" else self.order
+
+    def split(self, flat: torch.Tensor, which: str = "grad") -> Dict[str, torch.Tensor]:
+        """{name: view of `flat` in the parameter's shape} for the gradient region's parameters ("grad":
+        gradients, moments) or every parameter ("all": the SWA average).  `flat` is an arena-shaped buffer
+        or a host copy of one: the views cost nothing, so one device -> host copy serves every parameter."""
+        out = {}
+        for n in self._names(which):
+            p, o = self.params[n], self.offsets[n]
+            out[n] = flat[o:o + p.numel()].view(p.shape)
+        return out
+
+    def join(self, by_name, which: str = "grad", what: str = "tensor") -> torch.Tensor:
+        """the inverse of split(): a host fp32 buffer of the region's length (the gradient region's or the
+        whole arena's) with every parameter's tensor at its offset and zero alignment padding.  Strict: a
+        missing or unknown name or a different shape raises ValueError naming the first offender, before
+        anything is written anywhere."""
+        names = self._names(which)
+        for n in names:
+            if n not in by_name:
+                raise ValueError(f"{what}: no entry for parameter {n!r}")
+            if tuple(by_name[n].shape) != tuple(self.params[n].shape):
+                raise ValueError(f"{what}: parameter {n!r} has shape {tuple(by_name[n].shape)} in the file, "
+                                 f"{tuple(self.params[n].shape)} in the model")
+        known = set(names)
+        for n in by_name:
+            if n not in known:
+                raise ValueError(f"{what}: the file's parameter {n!r} is not in the model's "
+                                 f"{'gradient arena' if which == 'grad' else 'arena'}")
+        flat = torch.zeros(max(self.n_grad, 1) if which == "grad" else self.total, dtype=torch.float32)
+        for n in names:
+            o = self.offsets[n]
+            flat[o:o + self.params[n].numel()] = by_name[n].detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+        return flat
+
+    def trainable_names(self) -> List[str]:
+        """the reference optimizer's parameter list, [p for p in model.parameters() if p.requires_grad]
+        (reference training/trainer.py:120-130), by name and in that order"""
+        return [n for n, p in self.params.items() if p.requires_grad]
+
     def zero_grad(self):
         self.grad.zero_()
 

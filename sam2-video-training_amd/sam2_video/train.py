@@ -4,6 +4,7 @@ Lightning and W&B are not installed:
     python -m sam2_video.train --config-dir /path/to/configs --config-name best \\
         trainer.max_steps=100 data.train_path=... [+key=value ...]
     python -m sam2_video.train --config-json composed.json [key=value ...]   # an already composed tree
+    python -m sam2_video.train ... --resume PATH | --resume last              # continue a killed run exactly
 
 Composes the config (sam2_video.utils.config.compose: defaults list, interpolation,
 overrides), seeds, instantiates `module` and `data_module` with `_recursive_=False`, the
@@ -46,6 +47,9 @@ def main(argv=None, before_fit=None):
     ap.add_argument("--config-json", default=None,
                     help="a config tree composed beforehand (JSON); overrides still apply")
     ap.add_argument("--run-dir", default=None)
+    ap.add_argument("--resume", default=None, metavar="PATH",
+                    help="continue the run this checkpoint was taken from (Trainer.fit(ckpt_path=PATH)); "
+                         "'last' = <run_dir>/checkpoints/last.ckpt")
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args(argv)
     from .model.build import instantiate
@@ -57,6 +61,11 @@ def main(argv=None, before_fit=None):
             cfg = apply_overrides(json.load(f), args.overrides)
     else:
         cfg = compose(args.config_dir, args.config_name, args.overrides, run_dir=run_dir)
+    resume = args.resume
+    if resume == "last":
+        resume = os.path.join(run_dir, "checkpoints", "last.ckpt")
+        if not os.path.isfile(resume):
+            raise FileNotFoundError(f"--resume last: {resume} does not exist")
     seed = int(cfg.get("seed", 42))
     random.seed(seed)
     torch.manual_seed(seed)
@@ -70,7 +79,7 @@ def main(argv=None, before_fit=None):
                           default_root_dir=os.path.join(run_dir, "lightning_logs"))
     if before_fit is not None:
         before_fit(module, data_module, trainer)
-    hist = trainer.fit(module, data_module)
+    hist = trainer.fit(module, data_module, ckpt_path=resume)
     ck = os.path.join(run_dir, "checkpoints")
     os.makedirs(ck, exist_ok=True)
     trainer.save_checkpoint(os.path.join(ck, "last.ckpt"), module)

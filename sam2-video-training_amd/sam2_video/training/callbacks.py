@@ -10,7 +10,8 @@ down from Lightning's documented behaviour and were not compared with Lightning 
 What a trainer must offer (this build's Trainer does; tests drive the callbacks with a small fake):
 `callback_metrics` (name -> float), `current_epoch`, `global_step`, `max_epochs`, `default_root_dir`,
 `should_stop`, `is_global_zero`, `save_checkpoint(path)`, and for StochasticWeightAveraging `current_lr()` /
-`set_epoch_lr(lr)`.  Hooks have Lightning's signature `hook(trainer, pl_module)`.
+`set_epoch_lr(lr)`.  Hooks have Lightning's signature `hook(trainer, pl_module)`.  A callback's `state_dict()`
+goes into every checkpoint under its `state_key`; a resumed fit hands it to `load_state_dict` after on_fit_start.
 """
 from __future__ import annotations
 
@@ -38,6 +39,25 @@ class Callback:
         pass
 
     def on_train_end(self, trainer, pl_module):
+        pass
+
+    # ---- state in a checkpoint (Trainer.save_checkpoint writes {state_key: state_dict()} of every callback
+    # whose state is not empty; a resumed fit calls load_state_dict after on_fit_start)
+    @property
+    def state_key(self) -> str:
+        """what the state is filed under: the class name, plus the arguments that tell two callbacks of a
+        class apart (_state_key)"""
+        return type(self).__qualname__
+
+    @staticmethod
+    def _state_key(cls_name: str, **kw) -> str:
+        return f"{cls_name}{kw!r}"
+
+    def state_dict(self) -> dict:
+        """numbers, strings, lists and dicts only (the file loads with weights_only=True)"""
+        return {}
+
+    def load_state_dict(self, state: dict):
         pass
 
 
@@ -100,6 +120,7 @@ class ModelCheckpoint(Callback):
         self.best_model_path = ""
         self.best_model_score: Optional[float] = None
         self.last_model_path = ""
+        self.current_score: Optional[float] = None  # the monitored value of the latest validation
 
     # ---- names
     def format_checkpoint_name(self, metrics: Dict[str, float], ver: Optional[int] = None) -> str:
@@ -155,6 +176,7 @@ class ModelCheckpoint(Callback):
         metrics = self._candidates(trainer)
         if self.monitor is not None:
             current = _monitored(trainer, self.monitor, "ModelCheckpoint")
+            self.current_score = current
             if self.save_top_k != 0:
                 if math.isnan(current):
                     current = math.inf if self.mode == "min" else -math.inf
@@ -174,6 +196,37 @@ class ModelCheckpoint(Callback):
             self._save(trainer, path)
             if previous and previous != path:
                 self._remove(trainer, previous)
+
+    # ---- state
+    @property
+    def state_key(self) -> str:
+        return self._state_key(type(self).__qualname__, monitor=self.monitor, mode=self.mode, filename=self.filename)
+
+    def state_dict(self) -> dict:
+        return {"monitor": self.monitor, "best_model_score": self.best_model_score,
+                "best_model_path": self.best_model_path, "current_score": self.current_score,
+                "dirpath": self.dirpath, "best_k_models": dict(self.best_k_models),
+                "kth_best_model_path": self.kth_best_model_path, "kth_value": self.kth_value,
+                "last_model_path": self.last_model_path}
+
+    def load_state_dict(self, state: dict):
+        """the top-k books describe files in `dirpath`: they are taken over when the resumed run writes to the
+        same directory; with another one only best_model_path is (and a warning says so), and the new
+        directory starts its own list"""
+        saved_dir = state.get("dirpath", self.dirpath)
+        if self.dirpath == saved_dir:
+            self.best_model_score = state["best_model_score"]
+            self.kth_best_model_path = state.get("kth_best_model_path", self.kth_best_model_path)
+            self.kth_value = state.get("kth_value", self.kth_value)
+            self.best_k_models = dict(state.get("best_k_models", self.best_k_models))
+            self.last_model_path = state.get("last_model_path", self.last_model_path)
+            self.current_score = state.get("current_score", self.current_score)
+        else:
+            import warnings
+            warnings.warn(f"ModelCheckpoint: the checkpoint was written with dirpath={saved_dir!r}, this run uses "
+                          f"{self.dirpath!r}: best_model_score, best_k_models, kth_* and last_model_path are not "
+                          "restored", UserWarning, stacklevel=2)
+        self.best_model_path = state["best_model_path"]
 
     def _enters_top_k(self, current: float) -> bool:
         if self.save_top_k == -1 or len(self.best_k_models) < self.save_top_k:
@@ -220,6 +273,20 @@ class EarlyStopping(Callback):
         self.stopped_epoch = 0
         self.reason: Optional[str] = None
 
+    @property
+    def state_key(self) -> str:
+        return self._state_key(type(self).__qualname__, monitor=self.monitor, mode=self.mode)
+
+    def state_dict(self) -> dict:
+        return {"wait_count": self.wait_count, "stopped_epoch": self.stopped_epoch, "best_score": self.best_score,
+                "patience": self.patience}
+
+    def load_state_dict(self, state: dict):
+        self.wait_count = int(state["wait_count"])
+        self.stopped_epoch = int(state["stopped_epoch"])
+        self.best_score = float(state["best_score"])
+        self.patience = int(state["patience"])
+
     def _improved(self, current: float) -> bool:
         if self.mode == "min":
             return current < self.best_score - self.min_delta
@@ -265,6 +332,16 @@ class SWALRSchedule:
 
     def _alpha(self, t: float) -> float:
         return (1 - math.cos(math.pi * t)) / 2 if self.anneal_strategy == "cos" else t
+
+    def state_dict(self) -> dict:
+        return {"lr": self.lr, "swa_lr": self.swa_lr, "anneal_epochs": self.anneal_epochs,
+                "anneal_strategy": self.anneal_strategy, "_step_count": self._step_count}
+
+    @classmethod
+    def from_state(cls, state: dict) -> "SWALRSchedule":
+        sched = cls(state["lr"], state["swa_lr"], int(state["anneal_epochs"]), state["anneal_strategy"])
+        sched._step_count = int(state["_step_count"])
+        return sched
 
     def step(self) -> float:
         self._step_count += 1
@@ -350,6 +427,19 @@ class StochasticWeightAveraging(Callback):
     def on_train_epoch_end(self, trainer, pl_module):
         if self.schedule is not None:
             trainer.set_epoch_lr(self.schedule.step())
+
+    def state_dict(self) -> dict:
+        """the counters and the SWA schedule's position; the average itself (`arena.swa`) is a tensor of the
+        checkpoint's own block, written per parameter name by Trainer.save_checkpoint"""
+        return {"n_averaged": self.n_averaged, "_latest_update_epoch": self._latest_update_epoch,
+                "applied": self.applied, "schedule": None if self.schedule is None else self.schedule.state_dict()}
+
+    def load_state_dict(self, state: dict):
+        """after on_fit_start: swa_start / swa_end stay this run's own (a larger max_epochs moves swa_end)"""
+        self.n_averaged = int(state["n_averaged"])
+        self._latest_update_epoch = int(state["_latest_update_epoch"])
+        self.applied = bool(state["applied"])
+        self.schedule = None if state.get("schedule") is None else SWALRSchedule.from_state(state["schedule"])
 
     def on_train_end(self, trainer, pl_module):
         if self.n_averaged > 0 and self._latest_update_epoch == self.swa_end and not self.applied:

@@ -51,16 +51,100 @@ class ArenaAdamW:
     def zero_grad(self):
         self.arena.zero_grad()
 
+    # ---- state in torch.optim.AdamW's layout (the reference's optimizer under Lightning)
+    def _torch_group(self):
+        g = dict(_torch_adamw_defaults())
+        g.update(lr=self.param_groups[0]["lr"], betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
+                 amsgrad=False)
+        return g
+
     def state_dict(self):
+        """What `torch.optim.AdamW([p for p in model.parameters() if p.requires_grad], ...).state_dict()`
+        holds for the reference's optimizer: param_groups[0] with lr / betas / eps / weight_decay / amsgrad
+        False (and torch's other defaults) and params = [0..n); state[i] = {step, exp_avg, exp_avg_sq} in
+        the parameter's shape for the parameters inside the gradient arena -- the others never receive a
+        gradient, so torch has no state for them.  Before the first step torch has no state at all.  One
+        device -> host copy per moment buffer; the entries are host views of the two copies."""
         a = self.arena
-        return {"step": self.step_count, "exp_avg": a.exp_avg.detach().cpu(), "exp_avg_sq": a.exp_avg_sq.detach().cpu(),
-                "lr": self.param_groups[0]["lr"]}
+        names = a.trainable_names()
+        state = {}
+        if self.step_count > 0:
+            avg, sq = a.split(a.exp_avg.detach().cpu(), "grad"), a.split(a.exp_avg_sq.detach().cpu(), "grad")
+            for i, n in enumerate(names):
+                if n in avg:
+                    state[i] = {"step": torch.tensor(float(self.step_count)), "exp_avg": avg[n], "exp_avg_sq": sq[n]}
+        group = self._torch_group()
+        group["params"] = list(range(len(names)))
+        return {"state": state, "param_groups": [group]}
+
+    def plan_load(self, sd):
+        """Everything load_state_dict checks and builds, without touching the arena: (step, lr, exp_avg,
+        exp_avg_sq) with the two moments as host buffers of the gradient region's length, padding zero.
+        Accepts torch's layout (state / param_groups) and this class's earlier flat dict (step, lr, exp_avg
+        and exp_avg_sq of the arena's length).  What does not fit the trainable set raises ValueError naming
+        the first offender."""
+        a = self.arena
+        length = a.exp_avg.numel()
+        if "state" not in sd or "param_groups" not in sd:  # the flat dict of earlier files
+            for k in ("exp_avg", "exp_avg_sq"):
+                if tuple(sd[k].shape) != (length,):
+                    raise ValueError(f"optimizer state: flat {k} has {tuple(sd[k].shape)} elements, the gradient "
+                                     f"arena {length}")
+            return (int(sd["step"]), float(sd["lr"]), sd["exp_avg"].detach().float().cpu(),
+                    sd["exp_avg_sq"].detach().float().cpu())
+        names = a.trainable_names()
+        groups = sd["param_groups"]
+        n_file = sum(len(g["params"]) for g in groups)
+        if len(groups) != 1 or n_file != len(names):
+            first = names[n_file] if n_file < len(names) else f"index {len(names)} of the file"
+            raise ValueError(f"optimizer state: {n_file} parameters in {len(groups)} group(s) in the file, "
+                             f"{len(names)} trainable parameters in one group in the model (first without a "
+                             f"counterpart: {first})")
+        index = {int(i): n for i, n in zip(groups[0]["params"], names)}
+        in_arena = set(a.grad_names)
+        state = sd["state"]
+        avg, sq, steps = {}, {}, {}
+        for i, st in state.items():
+            n = index.get(int(i))
+            if n is None:
+                raise ValueError(f"optimizer state: index {i} is not in the file's param_groups")
+            if n not in in_arena:
+                raise ValueError(f"optimizer state: index {i} ({n}) has moments in the file, but the step never "
+                                 "gives it a gradient here (it is outside the gradient arena)")
+            avg[n], sq[n], steps[n] = st["exp_avg"], st["exp_avg_sq"], int(float(st["step"]))
+        if not state:
+            zeros = torch.zeros(length, dtype=torch.float32)
+            return 0, float(groups[0]["lr"]), zeros, zeros.clone()
+        flat_avg = a.join(avg, "grad", "optimizer state exp_avg")
+        flat_sq = a.join(sq, "grad", "optimizer state exp_avg_sq")
+        step = steps[a.grad_names[0]]
+        for n in a.grad_names:
+            if steps[n] != step:
+                raise ValueError(f"optimizer state: parameter {n!r} is at step {steps[n]}, {a.grad_names[0]!r} at "
+                                 f"{step}; the arena AdamW keeps one step count")
+        return step, float(groups[0]["lr"]), flat_avg, flat_sq
+
+    def apply_load(self, plan):
+        step, lr, avg, sq = plan
+        self.arena.exp_avg.copy_(avg)
+        self.arena.exp_avg_sq.copy_(sq)
+        self.step_count = int(step)
+        self.param_groups[0]["lr"] = float(lr)
 
     def load_state_dict(self, sd):
-        self.step_count = int(sd["step"])
-        self.arena.exp_avg.copy_(sd["exp_avg"])
-        self.arena.exp_avg_sq.copy_(sd["exp_avg_sq"])
-        self.param_groups[0]["lr"] = float(sd["lr"])
+        self.apply_load(self.plan_load(sd))
+
+
+_TORCH_DEFAULTS = {}
+
+
+def _torch_adamw_defaults():
+    """the keys a param group of this torch's AdamW carries besides `params` (maximize, foreach, capturable,
+    ...: they differ between torch versions, and a loaded group that misses one breaks torch's step)"""
+    if not _TORCH_DEFAULTS:
+        g = torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))]).param_groups[0]
+        _TORCH_DEFAULTS.update({k: v for k, v in g.items() if k != "params"})
+    return _TORCH_DEFAULTS
 
 
 def cosine_with_warmup(base_lr, num_warmup_steps, num_training_steps, num_cycles=0.5):
@@ -94,7 +178,7 @@ class ArenaOptimizer(torch.optim.Optimizer):
       graph-replayed micro-step, or by the module's backward hook (reduce_now) -- and the 1/world
       average is folded into the step's gradient scale;
     * the learning rate is param_groups[0]["lr"] (a torch LambdaLR drives it);
-    * state_dict carries the arena moments (Lightning checkpoints)."""
+    * state_dict carries the arena moments in torch.optim.AdamW's layout (Lightning checkpoints)."""
 
     def __init__(self, arena, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_grad_norm=0.0):
         params = list(params)
@@ -166,5 +250,6 @@ class ArenaOptimizer(torch.optim.Optimizer):
 
     def load_state_dict(self, sd):
         self.impl.load_state_dict(sd)
-        for g, lr in zip(self.param_groups, sd.get("param_groups_lr", [])):
+        lrs = sd.get("param_groups_lr") or [self.impl.param_groups[0]["lr"]] * len(self.param_groups)
+        for g, lr in zip(self.param_groups, lrs):
             g["lr"] = lr

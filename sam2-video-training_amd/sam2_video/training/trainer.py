@@ -23,6 +23,9 @@ sam2_video/training/trainer.py:28-400) and a Lightning-API Trainer for them.
   on_validation_end (after every validation but the sanity one),
   on_train_epoch_end and on_train_end; `callback_metrics`, `should_stop`,
   `checkpoint_callback` and `early_stopping_callback` are Lightning's attributes.
+  `fit(..., ckpt_path=PATH)` continues the run a checkpoint of `save_checkpoint` was taken from, bit for bit
+  (training/resume.py); a Lightning / reference checkpoint restores weights, optimizer state,
+  global_step and epoch.
 * `StepRunner`: one micro-step of the fit loop on the device (captured HIP
   graph per input signature), RCCL all-reduce + clip + AdamW at accumulation
   boundaries.
@@ -796,7 +799,10 @@ class Trainer:
         return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
 
     def _call_hook(self, hook):
-        for cb in self.callbacks:
+        """checkpoint callbacks go last (Lightning's order too), so the file one of them writes holds the
+        other callbacks' state after they saw the same event"""
+        from .callbacks import ModelCheckpoint
+        for cb in sorted(self.callbacks, key=lambda cb: isinstance(cb, ModelCheckpoint)):
             fn = getattr(cb, hook, None)
             if fn is not None:
                 fn(self, self.module)
@@ -850,7 +856,13 @@ class Trainer:
         t /= dist.get_world_size()
         return dict(zip(keys, t.tolist()))
 
-    def fit(self, module: SAM2LightningModule, datamodule=None, train_dataloaders=None, val_dataloaders=None):
+    def fit(self, module: SAM2LightningModule, datamodule=None, train_dataloaders=None, val_dataloaders=None,
+            ckpt_path=None):
+        """`ckpt_path` (Lightning's argument): continue the run a checkpoint of save_checkpoint was taken from,
+        bit for bit (DESIGN.md §9 lists what is restored and why); a checkpoint without this build's resume block
+        -- a Lightning / reference file -- restores weights, optimizer state, global_step and epoch, and the data
+        starts at the beginning of that epoch.  What does not fit raises ValueError before the arena is written."""
+        from . import resume as R
         from .ddp import init_from_env
         rank, world, local = init_from_env("nccl")
         device = torch.device("cuda", local)
@@ -875,27 +887,67 @@ class Trainer:
                          accumulate_grad_batches=self.accumulate_grad_batches,
                          gradient_clip_val=self.gradient_clip_val)
         self.runner = run
-        self._call_hook("on_fit_start")
+        self._batches_done, self._epoch_finished, self._rng_epoch_start = 0, False, None
+        # every check of the checkpoint, then weights / optimizer / counters / an open window's gradients: before
+        # on_fit_start, before anything is captured
+        plan = self._plan_resume(ckpt_path, module, run, rank, world) if ckpt_path is not None else None
+        if plan is not None:
+            self._apply_resume(plan, module, run)
+        self._call_hook("on_fit_start")  # (StochasticWeightAveraging allocates arena.swa here)
+        if plan is not None:
+            self._restore_callbacks(plan, module)
+        if plan is not None and plan["complete"]:
+            self._restore_books(plan)
+            import warnings
+            warnings.warn(f"Trainer.fit(ckpt_path={str(ckpt_path)!r}): the checkpoint's run is complete (epoch "
+                          f"{plan['epoch']}, global_step {self.global_step}; max_epochs {self.max_epochs}, max_steps "
+                          f"{self.max_steps}): nothing is trained", UserWarning, stacklevel=2)
+            return self.history
         if n_val and self.num_sanity_val_steps:  # (the sanity validation triggers no callback)
             self._validate(module, val_dataloaders, device, min(n_val, self.num_sanity_val_steps))
             self.val_history.clear()
             self.callback_metrics.clear()
+        start_epoch, skip = 0, 0
+        if plan is not None:
+            # after the sanity validation: its rows and its draws from the host generators leave no trace
+            self._restore_books(plan)
+            start_epoch, skip = plan["start_epoch"], plan["skip"]
+            if plan["rng"] is not None and not plan["mid_epoch"]:
+                R.set_host_rng_state(plan["rng"]["now"])
         vci = self.val_check_interval
         val_every = (max(1, int(n_train * vci)) if isinstance(vci, float) and vci <= 1.0 else int(vci)) if n_val else 0
         t0 = time.time()
         done = False
-        for epoch in range(self.max_epochs):
+        for epoch in range(start_epoch, self.max_epochs):
             self.current_epoch = epoch
             sampler = getattr(train_dataloaders, "sampler", None)
             if hasattr(sampler, "set_epoch"):
                 sampler.set_epoch(epoch)
-            self._call_hook("on_train_epoch_start")
-            for i, batch in enumerate(train_dataloaders):
+            self._epoch_finished = False
+            if plan is not None and plan["mid_epoch"] and epoch == start_epoch:
+                # the interrupted epoch (its on_train_epoch_start ran before the checkpoint was taken): the
+                # loader's iterator is created under the generator state the epoch started with, the consumed
+                # batches are skipped in the sampler, then the state of the moment of the checkpoint is put back
+                first = skip
+                if plan["rng"] is not None:
+                    self._rng_epoch_start = plan["rng"]["epoch_start"]
+                    torch.set_rng_state(self._rng_epoch_start)
+                batches = R.resumed_iterator(train_dataloaders, skip)
+                if plan["rng"] is not None:
+                    R.set_host_rng_state(plan["rng"]["now"])
+            else:
+                first = 0
+                self._batches_done = 0
+                self._call_hook("on_train_epoch_start")
+                self._rng_epoch_start = torch.get_rng_state()
+                batches = iter(train_dataloaders)
+            for i, batch in enumerate(batches, first):
                 if i >= n_train:
                     break
                 before = run.global_step
                 run(_to_device(batch, device))
                 self.global_step = run.global_step
+                self._batches_done = i + 1
                 if run.global_step != before and run.global_step % self.log_every_n_steps == 0:
                     row = {k: float(v) for k, v in module.logged.items() if k.startswith("train/")}
                     row["step"], row["epoch"], row["time_s"] = run.global_step, epoch, time.time() - t0
@@ -914,6 +966,7 @@ class Trainer:
                     break
             if not done and run.flush():  # the epoch's last, partial accumulation window
                 self.global_step = run.global_step
+            self._epoch_finished = not done
             self._train_metrics()
             self._call_hook("on_train_epoch_end")
             if done:
@@ -921,18 +974,178 @@ class Trainer:
         self._call_hook("on_train_end")
         return self.history
 
+    # ------------------------------------------------------------------- checkpoints
+    def _world(self):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            return dist.get_rank(), dist.get_world_size()
+        return 0, 1
+
+    def _resume_block(self, module):
+        """this build's own block of a checkpoint (None outside a fit): counters, the host generators of every
+        rank, an open accumulation window's partial sums of every rank, the SWA average, metrics and histories.
+        Arena-shaped tensors go per parameter name (ParamArena.split).  With more than one rank this gathers from
+        every rank, so every rank calls it; rank 0 gets the block, the others None."""
+        from . import resume as R
+        run = self.runner
+        if run is None or module is not self.module or getattr(getattr(module, "model", None), "arena", None) is None:
+            return None
+        arena = module.model.arena
+        rank, world = self._world()
+        mine = {"epoch_start": self._rng_epoch_start, "now": R.host_rng_state(), "grads": None}
+        if run.micro_step % run.accumulate:  # an open window: this rank's partial sums (not reduced yet)
+            mine["grads"] = arena.split(arena.grad.detach().cpu(), "grad")
+        ranks = [mine]
+        if world > 1:
+            import torch.distributed as dist
+            ranks = [None] * world
+            dist.all_gather_object(ranks, mine)
+        if rank != 0:
+            return None
+        return {"version": R.FORMAT_VERSION, "world_size": world, "accumulate": run.accumulate,
+                "micro_step": run.micro_step, "runner_global_step": run.global_step,
+                "batches_done": int(self._batches_done), "epoch_finished": bool(self._epoch_finished),
+                "seed_base": int(run.seed_base), "lr_override": run.lr_override,
+                "trainable": arena.trainable_names(), "ranks": ranks,
+                "swa": None if arena.swa is None else arena.split(arena.swa.detach().cpu(), "all"),
+                "callback_metrics": dict(self.callback_metrics), "history": [dict(r) for r in self.history],
+                "val_history": [dict(r) for r in self.val_history]}
+
     def save_checkpoint(self, path, module: Optional[SAM2LightningModule] = None):
         """Lightning-layout checkpoint: state_dict with the `model.` prefix (the reference strips it
-        when it reloads, train.py:146-157) + optimizer state + counters.  Written by global rank 0
-        only (Lightning's rank-zero checkpointing); the parameters are identical on every rank.
+        when it reloads, train.py:146-157), optimizer_states (torch.optim.AdamW's layout), lr_schedulers,
+        callbacks ({state_key: state}), global_step and epoch, plus -- during and after a fit -- the block
+        `s2h_resume` that fit(ckpt_path=...) needs for an exact resume.  Tensors, numbers, strings, lists and
+        dicts only: it loads with weights_only=True.  Written by global rank 0 only (Lightning's rank-zero
+        checkpointing; the parameters are identical on every rank), through a temporary file so that a job
+        killed while writing leaves the previous file whole; with more than one rank every rank calls it
+        (rank 0 collects the other ranks' generator states and open-window gradients).
         `module` defaults to the one being fitted (Lightning's trainer.save_checkpoint(path))."""
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
-            return
+        from . import resume as R
         module = self.module if module is None else module
+        block = self._resume_block(module)
+        if self._world()[0] != 0:
+            return
         sd = {"model." + k: v.detach().cpu() for k, v in module.model.state_dict().items()}
-        torch.save({"state_dict": sd, "optimizer_states": [module.optimizer.state_dict()],
-                    "global_step": self.global_step, "epoch": self.current_epoch}, path)
+        ck = {"state_dict": sd, "optimizer_states": [module.optimizer.state_dict()],
+              "global_step": self.global_step, "epoch": self.current_epoch, "lr_schedulers": [], "callbacks": {}}
+        if getattr(module, "lr_at", None) is not None:  # torch LambdaLR's state at this optimizer step
+            opt = module.optimizer
+            ck["lr_schedulers"] = [{"base_lrs": [opt.lr], "last_epoch": self.global_step,
+                                    "_step_count": self.global_step + 1, "lr_lambdas": [None],
+                                    "_last_lr": [opt.param_groups[0]["lr"]]}]
+        for cb in self.callbacks:
+            state = cb.state_dict() if hasattr(cb, "state_dict") else None
+            if state:
+                ck["callbacks"][getattr(cb, "state_key", type(cb).__qualname__)] = state
+        if block is not None:
+            ck[R.RESUME_KEY] = block
+        tmp = str(path) + ".part"
+        torch.save(ck, tmp)
+        os.replace(tmp, path)
+
+    def _plan_resume(self, ckpt_path, module, run, rank, world):
+        """reads the file (every rank does) and checks everything fit() will restore; ValueError on the first
+        thing that does not fit, with no device buffer written yet"""
+        import warnings
+
+        from . import resume as R
+        ck = torch.load(str(ckpt_path), map_location="cpu", weights_only=True)
+        model, opt = module.model, module.optimizer
+        arena = model.arena
+        block = ck.get(R.RESUME_KEY)
+        flat, others = R.plan_weights(model, model.strip_lightning_prefix(ck))
+        if block is not None:
+            if int(block["version"]) > R.FORMAT_VERSION:
+                raise ValueError(f"checkpoint resume block version {block['version']}: this build reads up to "
+                                 f"{R.FORMAT_VERSION}")
+            diff = R.first_difference(list(block["trainable"]), arena.trainable_names())
+            if diff is not None:
+                raise ValueError(f"checkpoint optimizer state does not fit the trainable set: {diff}")
+        states = ck.get("optimizer_states") or []
+        if len(states) != 1:
+            raise ValueError(f"checkpoint: {len(states)} optimizer states, this module has one optimizer")
+        plan = {"flat": flat, "others": others, "optimizer": opt.plan_load(states[0]), "callbacks": ck.get("callbacks") or {},
+                "epoch": int(ck["epoch"]), "global_step": int(ck["global_step"]), "block": block, "grads": None,
+                "swa": None, "rng": None, "mid_epoch": False, "skip": 0}
+        if block is None:
+            warnings.warn(f"Trainer.fit(ckpt_path={str(ckpt_path)!r}): no {R.RESUME_KEY} block (a Lightning / reference "
+                          "checkpoint): weights, optimizer state, global_step and epoch are restored; the position "
+                          f"inside epoch {plan['epoch']} is not known, its data starts from the beginning",
+                          UserWarning, stacklevel=3)
+            plan.update(start_epoch=plan["epoch"], micro_step=plan["global_step"] * run.accumulate,
+                        runner_global_step=plan["global_step"])
+        else:
+            micro, acc = int(block["micro_step"]), int(block["accumulate"])
+            mid_epoch, mid_window = not block["epoch_finished"], micro % acc != 0
+            if mid_epoch or mid_window:
+                where = "inside an epoch" if mid_epoch else "inside an accumulation window"
+                if int(block["world_size"]) != world:
+                    raise ValueError(f"checkpoint taken {where} with world size {block['world_size']}, this run "
+                                     f"has {world}")
+                if acc != run.accumulate:
+                    raise ValueError(f"checkpoint taken {where} with accumulate_grad_batches={acc}, this run has "
+                                     f"{run.accumulate}")
+            mine = block["ranks"][rank] if rank < len(block["ranks"]) else None
+            if mid_window:
+                plan["grads"] = arena.join(mine["grads"], "grad", "checkpoint open-window gradients")
+            if block.get("swa") is not None:
+                plan["swa"] = arena.join(block["swa"], "all", "checkpoint SWA average")
+            if mine is not None and int(block["world_size"]) == world:
+                plan["rng"] = mine  # (another world size at an epoch boundary: the generators stay as they are)
+            plan.update(mid_epoch=mid_epoch, skip=int(block["batches_done"]) if mid_epoch else 0,
+                        start_epoch=plan["epoch"] if mid_epoch else plan["epoch"] + 1,
+                        micro_step=micro if acc == run.accumulate else int(block["runner_global_step"]) * run.accumulate,
+                        runner_global_step=int(block["runner_global_step"]))
+        plan["complete"] = (plan["start_epoch"] >= self.max_epochs
+                            or (self.max_steps > 0 and plan["global_step"] >= self.max_steps))
+        return plan
+
+    def _apply_resume(self, plan, module, run):
+        """weights in place (parameter views, compute views and later captures stay valid) + shadow, moments,
+        step count and rate, counters, and an open window's partial sums, which the next micro-step adds to"""
+        arena = module.model.arena
+        with torch.no_grad():
+            arena.data.copy_(plan["flat"])
+            for own, value in plan["others"]:
+                own.copy_(value.to(own.dtype))
+            arena.refresh_shadow()
+            module.optimizer.apply_load(plan["optimizer"])
+            arena.zero_grad()
+            if plan["grads"] is not None:
+                arena.grad.copy_(plan["grads"])
+        self.global_step, self.current_epoch = plan["global_step"], plan["epoch"]
+        run.global_step, run.micro_step = plan["runner_global_step"], plan["micro_step"]
+        block = plan["block"]
+        if block is not None:
+            run.seed_base = int(block["seed_base"])
+            run.lr_override = None if block["lr_override"] is None else float(block["lr_override"])
+            self._batches_done, self._epoch_finished = int(block["batches_done"]), bool(block["epoch_finished"])
+
+    def _restore_callbacks(self, plan, module):
+        import warnings
+        saved = plan["callbacks"]
+        for cb in self.callbacks:
+            if not hasattr(cb, "load_state_dict"):
+                continue
+            key = getattr(cb, "state_key", type(cb).__qualname__)
+            if key in saved:
+                cb.load_state_dict(saved[key])
+            elif cb.state_dict():
+                warnings.warn(f"Trainer.fit(ckpt_path=...): the checkpoint has no state for the callback {key}; it "
+                              "starts fresh", UserWarning, stacklevel=3)
+        arena = module.model.arena
+        if plan["swa"] is not None and arena.swa is not None:
+            arena.swa.copy_(plan["swa"])
+
+    def _restore_books(self, plan):
+        block = plan["block"]
+        if block is None:
+            return
+        self.callback_metrics.clear()
+        self.callback_metrics.update(block["callback_metrics"])
+        self.history[:] = [dict(r) for r in block["history"]]
+        self.val_history[:] = [dict(r) for r in block["val_history"]]
 
 
 def fit(module: SAM2LightningModule, batches, max_steps: int, device="cuda", log_every: int = 1, distributed=False,
