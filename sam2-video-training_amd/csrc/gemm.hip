@@ -8,6 +8,8 @@
 // without transposed copies: each operand is either K-contiguous ("KC") or
 // M/N-contiguous, selected at compile time.  Tiles are staged through LDS in a
 // K-contiguous [row][k] image so both MFMA operands read 16-B fragments.
+#include <utility>
+
 #include "gemm_bf16.h"
 
 struct GemmArgs {
@@ -171,25 +173,20 @@ static int launch_gemm_tiles(const GemmArgs& a, int batch, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-static int g_gemm32_small = 1;  // A/B knob (s2h_gemm_f32_small): fp32 GEMMs of < 64 tiles on 32 x 32 tiles
-extern "C" int s2h_gemm_f32_small(int mode) {
-  const int prev = g_gemm32_small;
-  if (mode >= 0) g_gemm32_small = mode;
-  return prev;
+extern "C" int s2h_gemm_f32_small(int mode) {  // A/B knob: fp32 GEMMs of < 64 tiles on 32 x 32 tiles
+  return std::exchange(g_gemm_knobs.f32_small, mode >= 0 ? mode : g_gemm_knobs.f32_small);
 }
 
-template <typename T, typename TC>
-static int launch_gemm(const GemmArgs& a, int batch, hipStream_t st) {
-  // Small problems: 64x64 tiles keep enough workgroups in flight on 256 CUs.
-  long tiles128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128) * batch;
-  if (tiles128 >= 512) return launch_gemm_tiles<T, TC, 128, 128>(a, batch, st);
-  // fp32 problems of fewer than 64 tiles of 64^2 (the V-fold weight gradients dWo += G V^T, 256 x 256 x 72,
-  // and dV = Wo^T G, 256 x 72 x 256, once per layer and step): 32 x 32 tiles, 4x the workgroups
-  if constexpr (sizeof(T) == 4) {
-    const long tiles64 = (long)((a.M + 63) / 64) * ((a.N + 63) / 64) * batch;
-    if (g_gemm32_small && tiles64 < 64) return launch_gemm_tiles<T, TC, 32, 32>(a, batch, st);
+// the fp32 kernel on the plan's tile (gemm_plan.h gemm_f32_tile)
+static int launch_gemm_f32(const GemmArgs& a, int batch, hipStream_t st) {
+  GemmProblem p = {};
+  p.batch = batch; p.M = a.M; p.N = a.N; p.K = a.K;
+  p.f32_in = p.f32_out = true;
+  switch (gemm_plan(p, g_gemm_knobs, 0).tile.BM) {
+    case 128: return launch_gemm_tiles<float, float, 128, 128>(a, batch, st);
+    case 32: return launch_gemm_tiles<float, float, 32, 32>(a, batch, st);
+    default: return launch_gemm_tiles<float, float, 64, 64>(a, batch, st);
   }
-  return launch_gemm_tiles<T, TC, 64, 64>(a, batch, st);
 }
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -231,7 +228,7 @@ extern "C" int s2h_gemm(int dt_ab, int dt_c, int batch, int M, int N, int K,
   const int slot = s2h_prof_begin(stream, 4, batch, M, N, K, 2 * (lda_k == 1) + (ldb_k == 1) + 4 * (dt_ab == S2H_BF16));
   int rc;
   if (dt_ab == S2H_F32) {
-    rc = launch_gemm<float, float>(a, batch, stream);
+    rc = launch_gemm_f32(a, batch, stream);
     s2h_prof_end(slot, stream);
     return rc;
   }
@@ -282,6 +279,12 @@ extern "C" int s2h_linear_rope(int M, int N, int K, const void* A, int64_t lda, 
   return rc;
 }
 
+// the full-row tiling's plan for the two LayerNorm-epilogue entries below (their argument checks are the
+// LDS-DMA path's requirements; no forced tiling applies to them)
+static GemmPlan gemm_plan_full_row(const GemmArgs16Ln& b) {
+  return gemm_plan_glds(gemm_problem(b, 1), g_gemm_knobs, s2h_ws_registered_bytes(), gemm_full_row_cfg(b.N, b.K));
+}
+
 // Projection + dropout + residual + LayerNorm in one launch (bf16; round 4):
 //   X' = R + drop(A W^T + bias)   (C, the residual stream)      Y = LN(X') * gamma + beta
 // with mean / rstd per row -- a Linear followed by the residual add + LayerNorm that reads it
@@ -309,8 +312,7 @@ extern "C" int s2h_linear_add_ln(int M, int N, int K, const void* A, int64_t lda
   b.alpha = 1.f;
   b.vecA = 1; b.vecB = 1;
   b.ln_gamma = gamma; b.ln_beta = beta; b.ln_eps = eps; b.ln_y = Y; b.ln_ldy = ldy; b.ln_mean = mean; b.ln_rstd = rstd;
-  const int cfg = N == 128 ? CFG_64x128_W41_NS4 : (K <= 256 ? CFG_64x256_W41_NS4 : CFG_64x256_W41_NS3);
-  const int rc = gemm_cfg_launch_6_ln(cfg, b, 1, stream);
+  const int rc = gemm_cfg_launch_6_ln(gemm_plan_full_row(b), b, 1, stream);
   s2h_prof_end(slot, stream);
   return rc;
 }
@@ -349,8 +351,7 @@ extern "C" int s2h_linear_dgrad_ln_bwd(int M, int N, int K, const void* G, int64
   b.vecA = 1; b.vecB = 1;
   b.ln_gamma = gamma; b.ln_mean = const_cast<float*>(mean); b.ln_rstd = const_cast<float*>(rstd);
   b.lnb_x = X; b.lnb_ldx = ldx; b.lnb_part = dgamma ? part : nullptr;
-  const int cfg = N == 128 ? CFG_64x128_W41_NS4 : (K <= 256 ? CFG_64x256_W41_NS4 : CFG_64x256_W41_NS3);
-  int rc = gemm_cfg_launch_6_ln(cfg, b, 1, stream);
+  int rc = gemm_cfg_launch_6_ln(gemm_plan_full_row(b), b, 1, stream);
   s2h_prof_end(slot, stream);
   if (rc || !dgamma) return rc;
   return s2h_ln_wgrad_finalize((M + 63) / 64, N, part, dgamma, dbeta, stream);

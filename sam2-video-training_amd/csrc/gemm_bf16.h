@@ -1,6 +1,6 @@
 // bf16 MFMA GEMM for the compute path (fwd / dgrad / wgrad of every projection): the kernel
 // templates and their launchers.  The tilings are instantiated in gemm_cfg*.hip (one translation
-// unit per group, compiled in parallel); gemm_bf16.hip picks one per shape.
+// unit per group, compiled in parallel); gemm_plan.h picks one per shape, gemm_bf16.hip launches it.
 //
 // Each operand is staged into LDS in the layout its source already has, with
 // 16-B vector loads and 16-B LDS stores (no transposing scalar writes):
@@ -230,7 +230,7 @@ struct GImg {
       const int irow = piece * (1024 / RB) + lane / LPR;  // image row
       const int c = swz(irow, lane % LPR);                 // logical 16-B chunk held at this slot
       const bf16* src;
-      // 32-bit element offsets: gemm_glds_ok keeps operands past 2^31 elements on the
+      // 32-bit element offsets: gemm_glds_ok (gemm_plan.h) keeps operands past 2^31 elements on the
       // register-staged kernel (a 64-bit multiply per piece was a third of the step's VALU here)
       if (KC) {
         const int r = min(row0 + irow, nrows - 1);
@@ -455,7 +455,7 @@ void gemm16g_kernel(PA p) {
 // 32 KB at BN 64), so 4-5 workgroups fit a CU where the two-operand 64 x 64 tile with all K in flight
 // fits 2 (64 KB).  The A loads are plain (compiler-visible) loads issued before the B DMA: the one
 // wait before the first MFMA (vmcnt(0)) retires both.  Requirements: K-contiguous A, K <= KMAX,
-// no split-K, no fused row sums (gemm_areg_ok).
+// no split-K, no fused row sums (gemm_plan.h gemm_areg_ok).
 template <int BN, int KMAX, bool BKC>
 __global__ __launch_bounds__(256, 4) void gemm16a_kernel(GemmArgs16 p) {
   if (p.drop_p > 0.f) p.seed = s2h_seed(p.seed, p.seed_off);
@@ -518,78 +518,57 @@ __global__ __launch_bounds__(256, 4) void gemm16a_kernel(GemmArgs16 p) {
                                 lane);
 }
 
-static bool gemm_areg_ok(const GemmArgs16& a, int kmax) {
-  return a.lda_k == 1 && a.K <= kmax && a.K > 0 && a.rowsum == nullptr && ((uintptr_t)a.A & 15) == 0 &&
-         a.lda_m % 8 == 0 && a.K % 8 == 0 && (a.sA % 8 == 0);
+// the dispatch's view of one call (gemm_plan.h): shapes, layout, epilogue and the alignment facts
+static GemmProblem gemm_problem(const GemmArgs16& a, int batch) {
+  GemmProblem p = {};
+  p.batch = batch; p.M = a.M; p.N = a.N; p.K = a.K;
+  p.a_kc = a.lda_k == 1; p.a_rc = a.lda_m == 1;
+  p.b_kc = a.ldb_k == 1; p.b_rc = a.ldb_n == 1;
+  p.f32_out = a.out_f32 != 0;
+  p.bias = a.bias != nullptr; p.R = a.R != nullptr; p.X = a.X != nullptr; p.cscale = a.cscale != nullptr;
+  p.dropout = a.drop_p != 0.f; p.act = a.act; p.beta = a.beta;
+  p.rowsum = a.rowsum != nullptr; p.rope = a.rope_cos != nullptr;
+  p.lda = p.a_kc ? a.lda_m : a.lda_k;
+  p.ldb = p.b_kc ? a.ldb_n : a.ldb_k;
+  p.a16 = ((uintptr_t)a.A & 15) == 0; p.b16 = ((uintptr_t)a.B & 15) == 0;
+  p.sa8 = a.sA % 8 == 0; p.sb8 = a.sB % 8 == 0;
+  return p;
 }
 
-static bool gemm_glds_ok(const GemmArgs16& a, int batch) {
-  auto al = [](const void* ptr) { return ((uintptr_t)ptr & 15) == 0; };
-  const bool akc = a.lda_k == 1, bkc = a.ldb_k == 1;
-  const int64_t lda = akc ? a.lda_m : a.lda_k, ldb = bkc ? a.ldb_n : a.ldb_k;
-  const int aext = akc ? a.K : a.M, bext = bkc ? a.K : a.N;  // contiguous extents
-  // per-batch operand extents addressed with 32-bit element offsets in GImg::dma
-  const int64_t aspan = akc ? (int64_t)a.M * lda : (int64_t)a.K * lda;
-  const int64_t bspan = bkc ? (int64_t)a.N * ldb : (int64_t)a.K * ldb;
-  return al(a.A) && al(a.B) && lda % 8 == 0 && ldb % 8 == 0 && aext % 8 == 0 && bext % 8 == 0 &&
-         (batch == 1 || (a.sA % 8 == 0 && a.sB % 8 == 0)) && a.K > 0 && aspan < (1ll << 31) &&
-         bspan < (1ll << 31);
-}
-
-// weight gradients over a long reduction, deterministic split-K (gemm_wgrad.hip); -1: not its case
-int s2h_gemm_wgrad_det(const GemmArgs16& a, int batch, hipStream_t st);
-
-// workgroups a split-K launch aims at (s2h_gemm_split_target; gemm_bf16.hip)
-extern int g_gemm_split_target;
+// The one GemmKnobs instance (gemm_bf16.hip) and the registered workspace's size in bytes (gemm_wgrad.hip;
+// 0: none), the two inputs of gemm_plan beside the problem
+extern GemmKnobs g_gemm_knobs;
+int64_t s2h_ws_registered_bytes();
 
 // the second launch of a split launch with partial tiles (gemm16.h): C (beta 0 / 1) and rowsum get the
 // splits' sums in split order (gemm_bf16.hip)
 int s2h_gemm_split_reduce(const GemmArgs16& a, int batch, hipStream_t st);
 
-// split-K decision + output-group alignment for a BM x BN tiling
-static void plan_splits(GemmArgs16& a, int batch, int BM, int BN, hipStream_t st) {
-  const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * batch;
-  a.splits = 1;
-  a.kchunk = a.K;
-  const bool plain = a.out_f32 && !a.bias && !a.R && !a.X && !a.cscale && a.drop_p == 0.f && a.act == 0 &&
-                     (a.beta == 1.f || a.beta == 0.f);
-  if (plain && tiles < 512 && a.K >= 1024) {
-    int s = (g_gemm_split_target + tiles - 1) / tiles;
-    int maxs = a.K / 512;
-    if (s > maxs) s = maxs;
-    // up to 256 splits: the memory K / V projection weight gradients (256 x 64 over 374k rows)
-    // have 2-4 output tiles, which 64 splits left at half a wave of workgroups
-    if (s > 256) s = 256;
-    // deterministic (round 6): the splits' partial tiles in the workspace, added in split order by
-    // gemm_split_reduce_kernel -- the float atomics' arrival order made e.g. the hypernetwork-mask
-    // gradient (104 batched 1 x 32 x 65536 products, mask_decoder.py) differ between identical runs.
-    // As many splits as the workspace holds; none when it holds fewer than two.
-    const int64_t per = (int64_t)batch * a.M * a.N + (a.rowsum ? (int64_t)batch * a.M : 0);
-    const int64_t cap = (a.dbg & 32) ? 0 : s2h_det_ws_bytes() / 4;  // dbg 32: the atomic form (A/B)
-    if (cap > 0 && s > 1 && (int64_t)s * per > cap) s = (int)std::min<int64_t>(s, cap / per);
-    if (s > 1) {
-      a.splits = s;
-      a.kchunk = ((a.K + s - 1) / s + 63) / 64 * 64;
-      a.splits = (a.K + a.kchunk - 1) / a.kchunk;
-      if (cap > 0) {
-        a.X = s2h_det_ws((int64_t)a.splits * per * 4);
-        a.sX = (int64_t)batch * a.M * a.N;
-      } else if (a.beta == 0.f && a.ldc == a.N && (batch == 1 || a.sC == (int64_t)a.M * a.N)) {
-        s2h_zero_f32((float*)a.C, (int64_t)batch * a.M, a.N, a.N, st);
-      } else if (a.beta == 0.f) {
-        for (int b = 0; b < batch; ++b) s2h_zero_f32((float*)a.C + (int64_t)b * a.sC, a.M, a.N, a.ldc, st);
-      }
-    }
+// The plan's split-K side on the argument block: the K chunks, the partials' storage (or C zeroed for the
+// atomic form), the output-group alignment
+static void gemm_apply_plan(GemmArgs16& a, int batch, const GemmPlan& pl, hipStream_t st) {
+  a.splits = pl.splits;
+  a.kchunk = pl.kchunk;
+  if (pl.use_ws) {
+    a.X = s2h_det_ws(pl.ws_floats * 4);
+    a.sX = (int64_t)batch * a.M * a.N;
+  } else if (pl.zero_c && a.ldc == a.N && (batch == 1 || a.sC == (int64_t)a.M * a.N)) {
+    s2h_zero_f32((float*)a.C, (int64_t)batch * a.M, a.N, a.N, st);
+  } else if (pl.zero_c) {
+    for (int b = 0; b < batch; ++b) s2h_zero_f32((float*)a.C + (int64_t)b * a.sC, a.M, a.N, a.ldc, st);
   }
   gemm_plan_vec(a, batch);
 }
 
 template <int BM, int BN, int WGM, int WGN, int NS, int BK = 64, typename PA = GemmArgs16>
-static int launch_glds(PA& a, int batch, hipStream_t st) {
-  plan_splits(a, batch, BM, BN, st);
+static int launch_glds(const GemmPlan& pl, PA& a, int batch, hipStream_t st) {
+  const GemmTile& t = pl.tile;  // the plan was made for this instantiation's tile
+  if (t.BM != BM || t.BN != BN || t.WGM != WGM || t.WGN != WGN || t.NS != NS || t.BK != BK)
+    return (int)hipErrorInvalidConfiguration;
+  gemm_apply_plan(a, batch, pl, st);
   const bool akc = a.lda_k == 1, bkc = a.ldb_k == 1;
   constexpr int NT = GemmShape<BM, BN, WGM, WGN, NS, BK>::NT;
-  s2h_prof_tag(gemm_tag(BM, BN, WGM, WGN, NS, BK, akc, bkc, false, false));
+  s2h_prof_tag(pl.tag);
   dim3 g1(((a.N + BN - 1) / BN) * ((a.M + BM - 1) / BM), 1, batch * a.splits);
   if constexpr (std::is_same_v<PA, GemmArgs16Ln>) {
     if (akc && bkc) hipLaunchKernelGGL((gemm16g_kernel<BM, BN, WGM, WGN, NS, BK, true, true, GemmArgs16Ln>), g1, dim3(NT), 0, st, a);
@@ -607,17 +586,10 @@ static int launch_glds(PA& a, int batch, hipStream_t st) {
 }
 
 template <int BN, int KMAX = 256>
-static int launch_areg(GemmArgs16& a, int batch, hipStream_t st) {
-  plan_splits(a, batch, 64, BN, st);
-  if (a.splits != 1) {  // not this tiling's case: undo the plan for the caller's next launcher
-    a.splits = 1;
-    a.kchunk = a.K;
-    a.X = nullptr;
-    a.sX = 0;
-    return -1;
-  }
+static int launch_areg(const GemmPlan& pl, GemmArgs16& a, int batch, hipStream_t st) {
+  gemm_apply_plan(a, batch, pl, st);
   const bool bkc = a.ldb_k == 1;
-  s2h_prof_tag(gemm_tag(64, BN, 4, 1, 1, 64, true, bkc, false, false, true));
+  s2h_prof_tag(pl.tag);
   dim3 g(((a.N + BN - 1) / BN) * ((a.M + 63) / 64), 1, batch);
   if (bkc) hipLaunchKernelGGL((gemm16a_kernel<BN, KMAX, true>), g, dim3(256), 0, st, a);
   else hipLaunchKernelGGL((gemm16a_kernel<BN, KMAX, false>), g, dim3(256), 0, st, a);
@@ -625,10 +597,10 @@ static int launch_areg(GemmArgs16& a, int batch, hipStream_t st) {
 }
 
 template <int BM, int BN>
-static int launch16_regs(GemmArgs16& a, int batch, hipStream_t st) {
-  plan_splits(a, batch, BM, BN, st);
+static int launch16_regs(const GemmPlan& pl, GemmArgs16& a, int batch, hipStream_t st) {
+  gemm_apply_plan(a, batch, pl, st);
   const bool akc = a.lda_k == 1, bkc = a.ldb_k == 1;
-  s2h_prof_tag(gemm_tag(BM, BN, 2, 2, 1, 64, akc, bkc, true, false));
+  s2h_prof_tag(pl.tag);
   dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, batch * a.splits);
   if (akc && bkc) hipLaunchKernelGGL((gemm16_kernel<BM, BN, true, true>), grid, dim3(256), 0, st, a);
   else if (akc && !bkc) hipLaunchKernelGGL((gemm16_kernel<BM, BN, true, false>), grid, dim3(256), 0, st, a);
@@ -638,27 +610,16 @@ static int launch16_regs(GemmArgs16& a, int batch, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-// LDS-DMA tilings (s2h_gemm_config selects one for A/B measurements; 0 = automatic)
-enum GemmCfg {
-  CFG_AUTO = 0, CFG_64 = 1, CFG_128 = 2, CFG_128_NS3 = 3, CFG_256x128 = 4, CFG_256 = 5, CFG_128x256 = 6,
-  CFG_128x64 = 7, CFG_64x128 = 8, CFG_64_NS3 = 9, CFG_64_K32_NS4 = 10, CFG_128x64_K32_NS3 = 11,
-  CFG_128x64_K32_NS4 = 12, CFG_128x64_NS3 = 13, CFG_256x128_W4_K32_NS3 = 14, CFG_256x128_W4_K64 = 15,
-  CFG_128_K32_NS3 = 16, CFG_256x64_W4_K32_NS3 = 17, CFG_64_NS4 = 18, CFG_64_K32_NS8 = 19,
-  // 4 x 1 wave grids: every wave owns whole 64-column rows of the tile (128-B bf16 output rows)
-  CFG_64_W41 = 20, CFG_128x64_W41 = 21, CFG_128x64_W41_K32_NS3 = 22, CFG_64_W41_NS4 = 23, CFG_128x64_W41_NS3 = 24,
-  // full-row tiles (round 4): one workgroup owns 64 rows x the whole N <= 256 output width, the four
-  // waves stacked along M (16 full rows each), the K ring 4 stages deep (K <= 256 in one round trip)
-  CFG_64x256_W41_NS4 = 25, CFG_64x128_W41_NS4 = 26, CFG_64x256_W41_NS3 = 27, CFG_64x256_W41_K32_NS4 = 28,
-  // short K (round 4): A in registers, only B through LDS (gemm16a_kernel), K <= 256
-  CFG_64_AREG = 29, CFG_64x128_AREG = 30,
-  CFG_REGS = 99
-};
-// per-translation-unit launchers: return -1 when `cfg` is not one of the unit's tilings
-int gemm_cfg_launch_1(int cfg, GemmArgs16& a, int batch, hipStream_t st);
-int gemm_cfg_launch_2(int cfg, GemmArgs16& a, int batch, hipStream_t st);
-int gemm_cfg_launch_3(int cfg, GemmArgs16& a, int batch, hipStream_t st);
-int gemm_cfg_launch_4(int cfg, GemmArgs16& a, int batch, hipStream_t st);
-int gemm_cfg_launch_5(int cfg, GemmArgs16& a, int batch, hipStream_t st);
-int gemm_cfg_launch_6(int cfg, GemmArgs16& a, int batch, hipStream_t st);
-int gemm_cfg_launch_6_ln(int cfg, GemmArgs16Ln& a, int batch, hipStream_t st);  // the LayerNorm epilogues
-int gemm_cfg_launch_7(int cfg, GemmArgs16& a, int batch, hipStream_t st);
+// Per-translation-unit launchers of a finished plan: each takes the GemmCfg numbers it instantiates (s2h_gemm_bf16
+// calls the unit of plan.cfg; any other number is hipErrorInvalidValue)
+int gemm_cfg_launch_1(const GemmPlan& pl, GemmArgs16& a, int batch, hipStream_t st);  // 64-row 2 x 2 grids
+int gemm_cfg_launch_regs(const GemmPlan& pl, GemmArgs16& a, int batch, hipStream_t st);  // register-staged
+int gemm_cfg_launch_2(const GemmPlan& pl, GemmArgs16& a, int batch, hipStream_t st);
+int gemm_cfg_launch_3(const GemmPlan& pl, GemmArgs16& a, int batch, hipStream_t st);
+int gemm_cfg_launch_4(const GemmPlan& pl, GemmArgs16& a, int batch, hipStream_t st);
+int gemm_cfg_launch_5(const GemmPlan& pl, GemmArgs16& a, int batch, hipStream_t st);
+int gemm_cfg_launch_6(const GemmPlan& pl, GemmArgs16& a, int batch, hipStream_t st);
+int gemm_cfg_launch_6_ln(const GemmPlan& pl, GemmArgs16Ln& a, int batch, hipStream_t st);  // the LayerNorm epilogues
+int gemm_cfg_launch_7(const GemmPlan& pl, GemmArgs16& a, int batch, hipStream_t st);  // A in registers
+// weight gradients over a long reduction, deterministic split-K (gemm_wgrad.hip): a GEMM_WGRAD_DET plan
+int s2h_gemm_wgrad_det(const GemmPlan& pl, const GemmArgs16& a, hipStream_t st);

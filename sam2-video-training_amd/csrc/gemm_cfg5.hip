@@ -4,13 +4,13 @@
 // dominated the short-K forward GEMMs: tools/gemm_breakdown.py, profiles/r03_v10_*).
 #include "gemm_bf16.h"
 
-int gemm_cfg_launch_5(int cfg, GemmArgs16& a, int batch, hipStream_t st) {
-  switch (cfg) {
-    case CFG_64_W41: return launch_glds<64, 64, 4, 1, 2>(a, batch, st);
-    case CFG_128x64_W41: return launch_glds<128, 64, 4, 1, 2>(a, batch, st);
-    case CFG_128x64_W41_K32_NS3: return launch_glds<128, 64, 4, 1, 3, 32>(a, batch, st);
-    case CFG_64_W41_NS4: return launch_glds<64, 64, 4, 1, 4>(a, batch, st);
-    case CFG_128x64_W41_NS3: return launch_glds<128, 64, 4, 1, 3>(a, batch, st);
-    default: return -1;
+int gemm_cfg_launch_5(const GemmPlan& pl, GemmArgs16& a, int batch, hipStream_t st) {
+  switch (pl.cfg) {
+    case CFG_64_W41: return launch_glds<64, 64, 4, 1, 2>(pl, a, batch, st);
+    case CFG_128x64_W41: return launch_glds<128, 64, 4, 1, 2>(pl, a, batch, st);
+    case CFG_128x64_W41_K32_NS3: return launch_glds<128, 64, 4, 1, 3, 32>(pl, a, batch, st);
+    case CFG_64_W41_NS4: return launch_glds<64, 64, 4, 1, 4>(pl, a, batch, st);
+    case CFG_128x64_W41_NS3: return launch_glds<128, 64, 4, 1, 3>(pl, a, batch, st);
+    default: return (int)hipErrorInvalidValue;
   }
 }

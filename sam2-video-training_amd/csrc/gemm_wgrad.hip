@@ -247,16 +247,16 @@ static void wg_reduce_launch(const WgArgs& p, const GemmArgs16& a, hipStream_t s
                      (float*)a.C, a.ldc, a.alpha, a.beta, a.rowsum);
 }
 
-static float* g_wg_ws = nullptr;
-static int64_t g_wg_ws_bytes = 0;
-static int g_wg_kmin = 4096;  // reductions at least this long take the deterministic kernel (0: off)
-static int g_wg_force_tile = -1, g_wg_force_splits = 0;  // measurement override (s2h_wgrad_force)
+// the registered workspace (the settings that go with it -- kmin, the forced tile and split count -- are
+// g_gemm_knobs' wg_* fields, read by gemm_plan.h gemm_plan_wgrad)
+static float* g_ws = nullptr;
+static int64_t g_ws_bytes = 0;
 
 // Measurement knob (tools/wgrad_bench.py): force the tile (0 256x256, 1 256x128, 2 128x256, 3 128x128,
 // 4 256x64, 5 64x256; -1 = the cost model) and the split count (0 = the cost model's).  Returns 0.
 extern "C" int s2h_wgrad_force(int tile, int splits) {
-  g_wg_force_tile = tile;
-  g_wg_force_splits = splits;
+  g_gemm_knobs.wg_force_tile = tile;
+  g_gemm_knobs.wg_force_splits = splits;
   return 0;
 }
 
@@ -264,45 +264,38 @@ extern "C" int s2h_wgrad_force(int tile, int splits) {
 // unregisters it); kmin: the shortest reduction routed here (0 turns the kernel off, -1 keeps the
 // current value).  Returns 0 (hipSuccess).
 extern "C" int s2h_wgrad_workspace(void* ws, int64_t bytes, int kmin) {
-  g_wg_ws = (float*)ws;
-  g_wg_ws_bytes = ws ? bytes : 0;
-  if (kmin >= 0) g_wg_kmin = kmin;
+  g_ws = (float*)ws;
+  g_ws_bytes = ws ? bytes : 0;
+  if (kmin >= 0) g_gemm_knobs.wg_kmin = kmin;
   return 0;
 }
 
+int64_t s2h_ws_registered_bytes() { return g_ws_bytes; }
 float* s2h_det_ws(int64_t bytes) {
-  return (g_wg_kmin > 0 && g_wg_ws != nullptr && bytes <= g_wg_ws_bytes) ? g_wg_ws : nullptr;
+  return (g_gemm_knobs.wg_kmin > 0 && g_ws != nullptr && bytes <= g_ws_bytes) ? g_ws : nullptr;
 }
-int64_t s2h_det_ws_bytes() { return (g_wg_kmin > 0 && g_wg_ws != nullptr) ? g_wg_ws_bytes : 0; }
+int64_t s2h_det_ws_bytes() { return (g_gemm_knobs.wg_kmin > 0 && g_ws != nullptr) ? g_ws_bytes : 0; }
 
 template <int BM, int BN, int WGM, int WGN, int NS>
-static int wg_launch(const GemmArgs16& a, int Md, int Nd, int s, hipStream_t st) {
+static int wg_launch(const GemmPlan& pl, const GemmArgs16& a, hipStream_t st) {
+  const GemmTile& t = pl.tile;  // the plan (its workspace need) was made for this instantiation's tile
+  if (t.BM != BM || t.BN != BN || t.WGM != WGM || t.WGN != WGN || t.NS != NS) return (int)hipErrorInvalidConfiguration;
+  float* ws = s2h_det_ws(pl.ws_floats * 4);
   WgArgs p;
-  p.M = Md; p.N = Nd; p.K = a.K;
+  p.M = pl.Md; p.N = pl.Nd; p.K = a.K;
   p.Mo = a.M; p.No = a.N;
   p.A = a.A; p.lda = a.lda_k;
   p.B = a.B; p.ldb = a.ldb_k;
   p.ntm = (a.M + BM - 1) / BM;
   p.ntn = (a.N + BN - 1) / BN;
   const int tiles = p.ntm * p.ntn;
-  if (s < 1) s = 1;
-  const int64_t tile_bytes = (int64_t)BM * BN * 4;
-  const int64_t rs_bytes = a.rowsum ? (int64_t)p.ntm * BM * 4 : 0;
-  const int64_t fit = g_wg_ws_bytes / ((int64_t)tiles * tile_bytes + rs_bytes);
-  if (fit < 1) return -1;
-  if (s > fit) s = (int)fit;
-  p.kchunk = ((a.K + s - 1) / s + 63) / 64 * 64;
-  p.splits = (a.K + p.kchunk - 1) / p.kchunk;
-  p.part = g_wg_ws;
-  p.part_rs = a.rowsum ? g_wg_ws + (int64_t)p.splits * tiles * BM * BN : nullptr;
-  s2h_prof_tag(gemm_tag(BM, BN, WGM, WGN, NS, 64, false, false, false, false) | ((int64_t)1 << 41));
+  p.kchunk = pl.kchunk;
+  p.splits = pl.splits;
+  p.part = ws;
+  p.part_rs = a.rowsum ? ws + (int64_t)p.splits * tiles * BM * BN : nullptr;
+  s2h_prof_tag(pl.tag);
   hipLaunchKernelGGL((gemm_wg_kernel<BM, BN, WGM, WGN, NS>), dim3(tiles * p.splits), dim3(WGM * WGN * 64), 0, st, p);
-  // reduction: SL slices per slot so that about 2^17 threads (eight 16-B loads in flight each) read
-  // the partials
-  const int64_t slots = (int64_t)tiles * (BM * BN / 4);
-  int sl = 1;
-  while (sl < 16 && slots * sl < 131072 && sl * 2 <= p.splits) sl *= 2;
-  switch (sl) {
+  switch (pl.sl) {  // the reduce kernel's slices per slot
     case 16: wg_reduce_launch<BM, BN, WGM, WGN, 16>(p, a, st); break;
     case 8: wg_reduce_launch<BM, BN, WGM, WGN, 8>(p, a, st); break;
     case 4: wg_reduce_launch<BM, BN, WGM, WGN, 4>(p, a, st); break;
@@ -312,56 +305,16 @@ static int wg_launch(const GemmArgs16& a, int Md, int Nd, int s, hipStream_t st)
   return (int)hipGetLastError();
 }
 
-// -1: not this kernel's case (the caller's split-K path runs)
-int s2h_gemm_wgrad_det(const GemmArgs16& a, int batch, hipStream_t st) {
-  if (g_wg_kmin <= 0 || g_wg_ws == nullptr || batch != 1) return -1;
-  const bool plain = a.out_f32 && !a.bias && !a.R && !a.X && !a.cscale && a.drop_p == 0.f && a.act == 0 &&
-                     (a.beta == 1.f || a.beta == 0.f) && a.rope_cos == nullptr;
-  // every reduction the split-K path would split (plan_splits: < 512 tiles of 128 x 64, K >= 1024), and
-  // every reduction of >= kmin rows
-  const long t128x64 = (long)((a.M + 127) / 128) * ((a.N + 63) / 64);
-  // round 6: also the mid-length reductions (512 <= K < 1024) of few output tiles -- the two-way decoder's
-  // frame-batched weight gradients (832 token rows: 256 x 256, 256 x 2048, ...), which ran as 16-64
-  // unsplit 64 x 64 workgroups of 13 K steps (~23 us each, profiles/r06_v3_shape_table.txt)
-  const bool mid = a.K >= 512 && a.K < 1024 && t128x64 <= 64;
-  if (!plain || (a.K < 1024 && !mid) || (a.K < g_wg_kmin && t128x64 >= 512)) return -1;
-  if (a.lda_m != 1 || a.ldb_n != 1 || a.M < 16 || a.N < 64) return -1;
-  // operand extents rounded up to 8 inside the row pitch (the DMA moves 8-element pieces; the extra
-  // rows / columns are read, never stored)
-  const int Md = (a.M + 7) / 8 * 8, Nd = (a.N + 7) / 8 * 8;
-  if (Md > a.lda_k || Nd > a.ldb_k || a.lda_k % 8 || a.ldb_k % 8 || ((uintptr_t)a.A & 15) || ((uintptr_t)a.B & 15))
-    return -1;
-  if ((int64_t)a.K * a.lda_k >= (1ll << 31) - 8 || (int64_t)a.K * a.ldb_k >= (1ll << 31)) return -1;
-  // tile and split count from a cost model (one workgroup per CU): rounds of workgroups x (the
-  // K chunk's MFMA work at the tile's measured rate + a fixed prologue / epilogue) + the partial tiles
-  // written and read back once each.  Per-CU rates (TF/s) fitted to tools/wgrad_sweep.py
-  // (profiles/r05_v2_wgrad_sweep.log: the model's pick within ~10 % of the best forced tile x split).
-  struct Cand { int bm, bn; double rate; };
-  const Cand cands[] = {{256, 256, 4.2}, {256, 128, 3.4}, {128, 256, 3.4}, {128, 128, 2.4}, {256, 64, 2.0},
-                        {64, 256, 2.0}};
-  int best = -1, best_s = 1;
-  double best_t = 1e30;
-  for (int c = 0; c < 6; ++c) {
-    const int bm = cands[c].bm, bn = cands[c].bn;
-    const long tiles = (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn);
-    const int smax = std::max(1, std::min(256, a.K / (mid ? 128 : 512)));
-    for (int sp = 1; sp <= smax; ++sp) {
-      const long kchunk = ((a.K + sp - 1) / sp + 63) / 64 * 64;
-      const long wgs = tiles * sp;
-      const long rounds = (wgs + 255) / 256;
-      const double t = rounds * (2.0 * bm * bn * kchunk / (cands[c].rate * 1e6) + 2.5) +
-                       (sp > 1 ? 2.0 * wgs * bm * bn * 4 / 4.5e6 : 0.0);  // us
-      if (t < best_t) { best_t = t; best = c; best_s = sp; }
-    }
-  }
-  if (g_wg_force_tile >= 0 && g_wg_force_tile < 6) best = g_wg_force_tile;
-  if (g_wg_force_splits > 0) best_s = g_wg_force_splits;
-  switch (best) {
-    case 0: return wg_launch<256, 256, 2, 4, 2>(a, Md, Nd, best_s, st);
-    case 1: return wg_launch<256, 128, 4, 2, 2>(a, Md, Nd, best_s, st);
-    case 2: return wg_launch<128, 256, 2, 4, 2>(a, Md, Nd, best_s, st);
-    case 3: return wg_launch<128, 128, 2, 4, 3>(a, Md, Nd, best_s, st);
-    case 4: return wg_launch<256, 64, 4, 2, 3>(a, Md, Nd, best_s, st);
-    default: return wg_launch<64, 256, 1, 8, 3>(a, Md, Nd, best_s, st);
+// a GEMM_WGRAD_DET plan (gemm_plan.h gemm_plan_wgrad: eligibility, the cost model's tile and split count, the
+// workspace fit): the instantiation of gemm_wg_tile(pl.wg_tile)
+int s2h_gemm_wgrad_det(const GemmPlan& pl, const GemmArgs16& a, hipStream_t st) {
+  switch (pl.wg_tile) {
+    case 0: return wg_launch<256, 256, 2, 4, 2>(pl, a, st);
+    case 1: return wg_launch<256, 128, 4, 2, 2>(pl, a, st);
+    case 2: return wg_launch<128, 256, 2, 4, 2>(pl, a, st);
+    case 3: return wg_launch<128, 128, 2, 4, 3>(pl, a, st);
+    case 4: return wg_launch<256, 64, 4, 2, 3>(pl, a, st);
+    case 5: return wg_launch<64, 256, 1, 8, 3>(pl, a, st);
+    default: return (int)hipErrorInvalidValue;
   }
 }
