@@ -6,6 +6,7 @@
 // p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)).
 // Also: fp32 -> bf16 shadow-weight refresh for the bf16 compute path.
 #include "common.h"
+#include "optim_elem.h"
 
 // partial[b] = sum over block b of x^2
 // 16-B loads, four loads in flight per thread and four accumulator chains (the scalar grid-stride
@@ -52,14 +53,7 @@ __global__ __launch_bounds__(256) void norm_finalize_kernel(int nb, const float*
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float norm = sqrtf(red[0] + red[1] + red[2] + red[3]) * grad_scale;
-    out[0] = norm;
-    float c = 1.f;
-    if (max_norm > 0.f) {
-      c = max_norm / (norm + 1e-6f);
-      if (c > 1.f) c = 1.f;
-    }
-    out[1] = c * grad_scale;
+    oe_clip_pair(red[0] + red[1] + red[2] + red[3], max_norm, grad_scale, out);
   }
 }
 #define NORM_BLOCKS 1024
@@ -71,24 +65,14 @@ extern "C" int s2h_grad_norm(int64_t n, const float* g, float* partial_ws, float
   return (int)hipGetLastError();
 }
 
-// One element's AdamW update (torch.optim.AdamW, decoupled weight decay), every rounding step written
-// out (explicit fmaf) so the scalar and the 16-B kernels below produce the same bits for any compiler
-// contraction choice
-__device__ __forceinline__ void adamw_elem(float g, float& p, float& m, float& v, float cf, float decay, float w1,
-                                           float beta2, float omb2, float eps, float step_size, float bc2_sqrt) {
-  const float gi = g * cf;
-  const float mi = fmaf(w1, gi - m, m);
-  const float vi = fmaf(omb2, gi * gi, v * beta2);
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p = fmaf(-step_size, mi / denom, p * decay);
-  m = mi;
-  v = vi;
-}
+// One element's AdamW update is adamw_elem of optim_elem.h: every rounding step is written out there (products
+// rounded before they are added, explicit fmaf), so the scalar and the 16-B kernels below produce the same bits,
+// the bits of the header compiled for the host
 __global__ __launch_bounds__(256) void adamw_kernel(int64_t n, float* p, const float* g, float* m, float* v,
                                                     const float* clip, float lr, float beta1, float beta2, float eps,
                                                     float wd, float step_size, float bc2_sqrt, bf16* shadow) {
   const float cf = clip ? clip[1] : 1.f;
-  const float decay = 1.f - lr * wd, w1 = 1.f - beta1, omb2 = 1.f - beta2;
+  const float decay = oe_decay(lr, wd), w1 = oe_w1(beta1), omb2 = oe_omb2(beta2);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     float pi = p[i], mi = m[i], vi = v[i];
     adamw_elem(g[i], pi, mi, vi, cf, decay, w1, beta2, omb2, eps, step_size, bc2_sqrt);
@@ -103,7 +87,7 @@ __global__ __launch_bounds__(256) void adamw_vec_kernel(int64_t n4, float4* p, c
                                                         const float* clip, float lr, float beta1, float beta2, float eps,
                                                         float wd, float step_size, float bc2_sqrt, uint2* shadow) {
   const float cf = clip ? clip[1] : 1.f;
-  const float decay = 1.f - lr * wd, w1 = 1.f - beta1, omb2 = 1.f - beta2;
+  const float decay = oe_decay(lr, wd), w1 = oe_w1(beta1), omb2 = oe_omb2(beta2);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     const float4 g4 = g[i], p4 = p[i], m4 = m[i], v4 = v[i];
     const float ga[4] = {g4.x, g4.y, g4.z, g4.w};
@@ -123,10 +107,8 @@ __global__ __launch_bounds__(256) void adamw_vec_kernel(int64_t n4, float4* p, c
 extern "C" int s2h_adamw(int64_t n, float* p, const float* g, float* m, float* v, const float* clip, float lr,
                          float beta1, float beta2, float eps, float wd, int step, void* bf16_shadow, hipStream_t st) {
   if (n <= 0) return 0;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)(lr / bc1);
-  const float bc2_sqrt = (float)sqrt(bc2);
+  const float step_size = oe_step_size(lr, beta1, step);
+  const float bc2_sqrt = oe_bc2_sqrt(beta2, step);
   const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0 &&
                    ((uintptr_t)bf16_shadow & 7) == 0;
   const int64_t n4 = vec ? n / 4 : 0;

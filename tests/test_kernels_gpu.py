@@ -1073,7 +1073,10 @@ def test_relu_mask_bwd_from_output(dtype, p):
 def test_clip_adamw_matches_torch(max_norm, grad_scale):
     """s2h_grad_norm + s2h_adamw (ArenaAdamW) == clip_grad_norm_ + torch.optim.AdamW on the
     scaled gradient: grad_scale models the 1/world average after the SUM all-reduce (world 2 ->
-    0.5) and 1/accumulate_grad_batches; max_norm 0 = no clip (Lightning's gradient_clip_val 0)"""
+    0.5) and 1/accumulate_grad_batches; max_norm 0 = no clip (Lightning's gradient_clip_val 0).
+    With max_norm > 0 steps 1 and 2 clip (0.01 * randn(300 001) has norm 5.5, 3 * randn 1643) and step 3 does
+    not (1e-5 * randn: norm 5.5e-3, the coefficient is clamped at 1); test_optim_gpu.py pins the same kernels
+    bit for bit"""
     ops = _ops()
     torch.manual_seed(11)
     n = 300_001
@@ -1083,7 +1086,7 @@ def test_clip_adamw_matches_torch(max_norm, grad_scale):
     m, v = torch.zeros_like(p), torch.zeros_like(p)
     ws, out = torch.empty(1024, device=DEV), torch.zeros(2, device=DEV)
     for step in range(1, 4):
-        g = torch.randn(n, device=DEV) * (3.0 if step == 2 else 0.01)  # step 2 clips, the others do not
+        g = torch.randn(n, device=DEV) * {1: 0.01, 2: 3.0, 3: 1e-5}[step]
         pt.grad = g * grad_scale
         if max_norm > 0:
             torch.nn.utils.clip_grad_norm_([pt], max_norm)
@@ -1091,6 +1094,8 @@ def test_clip_adamw_matches_torch(max_norm, grad_scale):
         ops.grad_norm(g, max_norm, ws, out, grad_scale)
         ops.adamw(p, g, m, v, out, 1e-3, 0.9, 0.999, 1e-8, 0.01, step)
         _close(out[0:1], (g * grad_scale).norm().view(1), 1e-5)
+        if max_norm > 0:  # out[1] = grad_scale * coefficient: below grad_scale when the step clips
+            assert (float(out[1]) < grad_scale) == (step < 3) and (step < 3 or float(out[1]) == grad_scale)
     _close(p, pt.detach(), 1e-5)
 
 
