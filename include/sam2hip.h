@@ -796,6 +796,26 @@ int s2h_resample_u8_norm(int F, int H, int W, const uint8_t* src, int Sw, int kx
 int s2h_rle_catmasks(int F, int N, int H, int W, int A, const int* run_off, const int* run_end,
                      const int* ann_cat, const int* frame_off, int Sh, int Sw, const int* row_map,
                      const int* col_map, uint8_t* out, hipStream_t st);
+/* ---- dataset preparation (reference data/convert_endovis_to_coco.py:132-179 and
+ * data/apply_morphological_opening.py:57-72; csrc/dataprep.hip).  Both entries are pure functions of their inputs:
+ * integer arithmetic, no float, no 64-bit atomics, no host round trip, every device loop bounded by the sizes.
+ * Limits of s2h_rle_decode and s2h_rle_transitions: H, W >= 1, H * W <= 2^24, F * H * W and P * H * W
+ * < 2^31 - 256 (hipErrorInvalidValue otherwise).
+ *
+ * Per frame the pixel count of every byte value (np.unique / np.bincount of a label image).  labels [F, H, W]
+ * uint8, row-major; hist [F, 256] int32, zeroed by the call.  32-bit counters privatised per workgroup in LDS,
+ * then one integer atomic per non-zero counter. */
+int s2h_label_hist(int F, int H, int W, const uint8_t* labels, int* hist, hipStream_t st);
+/* Row-major label bytes -> the column-major bit words s2h_rle_transitions reads, one plane per (frame, class).
+ * Plane p belongs to frame f when frame_off[f] <= p < frame_off[f + 1] (frame_off [F + 1], CSR, ascending from 0
+ * to P); bits [P, ceil(H W / 64)]: bit j % 64 of word j / 64 of plane p = (labels[f][j % H][j / H] ==
+ * plane_class[p]), or (labels[f][j % H][j / H] != 0) when plane_class[p] == -1 (byte masks, e.g. after
+ * s2h_morph_rect: one frame and one plane per mask).  The layout is s2h_mask_export's; bits past H W are zero.
+ * Every word of every plane is written exactly once, and no plane outside [0, P) whatever frame_off holds.
+ * P == 0 returns without a launch.  A workgroup stages one frame's band of 64 columns in LDS (H * 64 bytes,
+ * H <= 2048) and builds every plane of the frame from it; taller images are read straight from memory. */
+int s2h_label_planes(int F, int H, int W, const uint8_t* labels, int P, const int* frame_off,
+                     const int* plane_class, uint64_t* bits, hipStream_t st);
 /* The first upscaling step in one pass (mask_decoder.py:105-106, bf16, Co = 64): pre = the s2h_convt2_store
  * values, y / mean / rstd = LayerNorm2d(pre) over the channels (gamma, beta, eps; the values of
  * s2h_layernorm_fwd), post = gelu(y) (as s2h_act_fwd rounds it); mean / rstd [B * 2H * 2W] fp32. */

@@ -31,8 +31,8 @@ csrc/cc.hip -- RLE decode, the 10 x 10 closing, labelling, the kept components w
 and the pixel of every drawn rank -- with two copies to the host; the random draws are the reference's
 np.random.choice calls in the reference's order, so both paths give the same prompts under the same seed.
 `on_device=False` is eval/utils.py mask_to_masks / mask_to_points, the A/B path.  The closing's window is
-eval/utils.py CLOSE_DILATE_WINDOW: it follows OpenCV's documented formulas and was not checked against an
-OpenCV binary.
+eval/utils.py CLOSE_DILATE_WINDOW: it follows OpenCV's documented formulas, and the masks the reference's own
+cv2 opening wrote agree with it ("Dataset preparation on the device").
 
 Out of scope: PromptObjNoiseAdder (`noised_prompt=True` raises: it needs albumentations) and the reference's
 dead helpers generate_negative_samples, fluctuate_point and get_obj_from_masks.

@@ -61,7 +61,11 @@ def sort_dicts_by_field(data, field_name, reverse=False):
 #     dilate: dst(x, y) = max over (x', y') of src(x + x' - anchor.x, y + y' - anchor.y)      erode: min over the same,
 # and the default anchor of an even window of 10 is 5: the offsets -5 .. 4 along either axis, for both.  These
 # constants hold (lo, hi) of that offset range, used for rows and columns alike.
-# Not verified against an OpenCV binary: cv2 is not a dependency of this package or of its tests.
+# cv2 is not a dependency of this package or of its tests, but the reference's own data settles the reading:
+# the 1285 masks its cv2.MORPH_OPEN with ones((10, 10)) wrote (data/endovis18_coco_annotations_val_opened.json)
+# are shifted by +1 in x and y against their pre-opening boxes, and are fixed points of
+# dilate(-5 .. 4) after erode(-4 .. 5) but not of dilate(-4 .. 5) after it at the image border -- DESIGN.md §9,
+# "Dataset preparation on the device"; tests/test_dataprep_host.py pins it on 24 of them.
 # The alternative reading -- a dilation by the REFLECTED window, offsets -4 .. 5, as the set-theoretic definition
 # of a Minkowski sum has it -- is CLOSE_DILATE_WINDOW = (-4, 5).  Away from the image border the two give the
 # same closed masks shifted by one pixel: the alternative's result is the default's moved by (-1, -1) in (x, y)

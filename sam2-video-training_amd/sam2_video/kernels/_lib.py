@@ -143,6 +143,8 @@ SIGNATURES = {
     "s2h_mask_export_cut": [I, I, I, I, I, P, I, P, P, I, F, P, P, P, P, P],
     "s2h_mask_sweep": [I, I, I, I, I, P, I, P, P, I, I, P, P, P, P],
     "s2h_rle_transitions": [I, I, I, P, I, P, P, P, P],
+    "s2h_label_hist": [I, I, I, P, P, P],
+    "s2h_label_planes": [I, I, I, P, I, P, P, P, P],
     "s2h_resample_u8_norm": [I, I, I, P, I, I, P, P, P, I, I, P, P, P, I, I, P, P, P, P],
     "s2h_rle_catmasks": [I, I, I, I, I, P, P, P, P, I, I, P, P, P, P],
     "s2h_convt2_ln_gelu": [I, I, I, I, I, P, P, P, I, P, P, F, P, P, P, P, P, P],

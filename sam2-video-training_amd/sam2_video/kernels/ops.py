@@ -1400,6 +1400,18 @@ def rle_decode(counts_list, H, W, device="cuda"):
     return mask
 
 
+def rle_decode_runs(run_off, run_end, H, W):
+    """rle_decode from run boundaries already on the device (int32, as rle_runs gives them) -> uint8 [A, H, W]"""
+    for t in (run_off, run_end):
+        assert t.dim() == 1 and t.dtype == torch.int32 and t.is_contiguous()
+    _dev(run_off, run_end)
+    A = run_off.numel() - 1
+    mask = torch.empty(A, int(H), int(W), device=run_off.device, dtype=torch.uint8)
+    if A > 0:
+        call("s2h_rle_decode", A, int(H), int(W), ptr(run_off), ptr(run_end), ptr(mask), stream())
+    return mask
+
+
 PC_MAX_GROUP_ANNS = 1 << 12  # csrc/pair_counts.h: annotations per group and side
 
 
@@ -1811,6 +1823,46 @@ def rle_transitions(bits, H, W, capacity=None, hdr=None, trans=None):
     work = torch.empty(max(1, 7 * ncat * ((nw + 255) // 256)), device=bits.device, dtype=torch.int32)
     call("s2h_rle_transitions", ncat, H, W, ptr(bits), capacity, ptr(hdr), ptr(trans), ptr(work), stream())
     return hdr, trans
+
+
+# ---------------------------------------------------------------------- dataset preparation (csrc/dataprep.hip)
+def label_hist(labels):
+    """per frame the pixel count of every byte value (s2h_label_hist): labels [F, H, W] uint8 contiguous on the
+    device -> int32 [F, 256]"""
+    assert labels.dim() == 3 and labels.dtype == torch.uint8 and labels.is_contiguous()
+    _dev(labels)
+    F, H, W = labels.shape
+    hist = torch.empty(F, 256, device=labels.device, dtype=torch.int32)
+    call("s2h_label_hist", F, H, W, ptr(labels), ptr(hist), stream())
+    return hist
+
+
+def label_planes(labels, frame_off, plane_class):
+    """row-major label bytes -> column-major bit words, one plane per (frame, class) (s2h_label_planes).
+    labels [F, H, W] uint8; frame_off [F + 1] int32 (CSR, ascending from 0 to P): the planes of frame f are
+    [frame_off[f], frame_off[f + 1]); plane_class [P] int32: plane p is labels[f] == plane_class[p], or
+    labels[f] != 0 for -1; all on the device.  -> int64 [P, ceil(H W / 64)] holding the uint64 words in the
+    layout of pack_mask_bits / mask_export, what rle_transitions reads."""
+    assert labels.dim() == 3 and labels.dtype == torch.uint8 and labels.is_contiguous()
+    for t in (frame_off, plane_class):
+        assert t.dim() == 1 and t.dtype == torch.int32 and t.is_contiguous()
+    _dev(labels, frame_off, plane_class)
+    F, H, W = labels.shape
+    P = plane_class.numel()
+    assert frame_off.numel() == F + 1
+    bits = torch.empty(P, rle_words(H, W), device=labels.device, dtype=torch.int64)
+    if P:
+        call("s2h_label_planes", F, H, W, ptr(labels), P, ptr(frame_off), ptr(plane_class), ptr(bits), stream())
+    return bits
+
+
+def mask_planes(mask_u8):
+    """byte masks [N, H, W] uint8 (nonzero = set, e.g. what morph_rect writes) -> their bit words int64
+    [N, ceil(H W / 64)]: label_planes with one plane of class -1 per mask"""
+    N = mask_u8.shape[0]
+    frame_off = torch.arange(N + 1, device=mask_u8.device, dtype=torch.int32)
+    plane_class = torch.full((N,), -1, device=mask_u8.device, dtype=torch.int32)
+    return label_planes(mask_u8, frame_off, plane_class)
 
 
 def convt2_gather(dout, B, H, W, Co, dY=None):
