@@ -46,8 +46,8 @@ Each constant is the smallest of 1, 2, 3 that keeps its figure under a quarter w
 output rounded to bf16 the clean model reaches 0.99 of rnd(v) by construction (a value half an ulp from a
 tie), so the quarter is asserted on the fp32 value and <= 1 on the rounded one.
 
-Not covered here: dt_layernorm (csrc/decoder_tok.hip) forms its input inside the launch; pinning it needs a
-harness of its own."""
+dt_layernorm (csrc/decoder_tok.hip) forms its input inside the launch: the same regimes and check_fwd reach it
+through dec_tok_cases.py, test_decoder_tok_host.py and test_decoder_tok_kernels_gpu.py."""
 import functools
 import math
 

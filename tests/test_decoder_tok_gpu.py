@@ -1,5 +1,7 @@
 """The two-way transformer's token side as fused launches (csrc/decoder_tok.hip, frametape.dec_self /
-dec_post / dec_final) against its separate launches (S2H_DEC_TOK=0) on a bf16 training step."""
+dec_post / dec_final) against its separate launches (S2H_DEC_TOK=0) on a bf16 training step.
+The kernel-level float64 pins of every stored stage are in test_decoder_tok_kernels_gpu.py; the step-level
+tests here stay as they are."""
 import pytest
 import torch
 

@@ -22,8 +22,8 @@ The tolerances are ln_cases.py's, fixed from the fp32 model on the CPU; test_lay
 proves that each assertion can fail by more than 10x.
 
 ops.layernorm_bwd passes ldx = lddy = lddx = C: a strided backward is unreachable from Python, so only the
-forward is run from strided rows.  Not covered: dt_layernorm (csrc/decoder_tok.hip) forms its input inside
-the launch; pinning it needs a harness of its own.
+forward is run from strided rows.  dt_layernorm (csrc/decoder_tok.hip) forms its input inside the launch: it
+is pinned on the same regimes by dec_tok_cases.py and test_decoder_tok_kernels_gpu.py.
 
 Observed maxima on an MI355X over all cases, as error / tolerance (the module prints them at teardown, -s).
 Where the output is bf16, y / dx / the GELU sit at 0.97 .. 0.99: the store's own rounding uses up to the
