@@ -816,6 +816,37 @@ int s2h_label_hist(int F, int H, int W, const uint8_t* labels, int* hist, hipStr
  * H <= 2048) and builds every plane of the frame from it; taller images are read straight from memory. */
 int s2h_label_planes(int F, int H, int W, const uint8_t* labels, int P, const int* frame_off,
                      const int* plane_class, uint64_t* bits, hipStream_t st);
+/* ---- training visualisation (reference utils/viz.py; csrc/viz.hip, the picture is csrc/viz_pixel.h).  Pure
+ * functions of their inputs, integer arithmetic but for the frame conversion (two separately rounded double
+ * operations), no atomics, no host round trip, one launch each whatever the data holds.
+ * Limits of both: 1 <= H, W; 1 <= C <= 64; n * 2H * 2W * 3 < 2^31 (hipErrorInvalidValue otherwise); n == 0
+ * returns without a launch.
+ *
+ * Category words: words [n, H W] uint64, bit c of words[f][p] = (src[f][c][p] > 0.5) -- the reference's rule for
+ * ground truth and raw logits alike.  kind 0: src uint8 / bool (set = non-zero), kind 1: fp32 (NaN = clear).
+ * Frame f's [C, H, W] block starts frame_stride elements after frame f - 1's (>= 0; C H W = contiguous frames), so
+ * every k-th frame of a clip is read where it lies.  Every word is written exactly once. */
+int s2h_viz_pack(int n, int C, int H, int W, int kind, const void* src, int64_t frame_stride, uint64_t* words,
+                 hipStream_t st);
+/* The n composites: out [n, 2H, 2W, 3] uint8 (4-byte aligned), every byte written exactly once, in whole dwords.
+ * Panels: top-left frame f, top-right frame f + the overlay of gt_words[f], bottom-left frame0 + prompts,
+ * bottom-right frame f + the overlay of pred_words[f].
+ * img_kind 0: frames fp32 [3, H, W] per frame, ImageNet-normalised, u = trunc(clamp((double)x * std_c + mean_c, 0, 1)
+ * * 255) (NaN -> 0); img_kind 1: uint8 [H, W, 3] passed through.  frame_stride (elements) as for s2h_viz_pack;
+ * frame0 = one frame of the same kind.
+ * Overlay panel: every pixel (4 base + overlay + 2) / 5 per channel with overlay = palette[highest set category]
+ * or 0 (cv2.addWeighted(base, 0.8, overlay, 0.2), pixels without a mask included); then, at full opacity,
+ * palette[highest category c whose 3 x 3 neighbourhood, positions outside the image ignored, holds both a pixel
+ * with c set and one with c clear].  palette [C, 3] uint8.
+ * Prompts: prompt_words [H W] non-null (mask prompts) = frame0 with that overlay, no markers.  Otherwise the M <= 256
+ * markers [M, 8] int32 {kind, x1, y1, x2, y2, r, g, b} in table order, later ones overwriting, clipped to the
+ * image: kind 0 disc at (x1, y1) -- colour where dx^2 + dy^2 < 49, white where 49 <= dx^2 + dy^2 <= 81; kind 1
+ * cross -- (|dx| <= 1 and |dy| <= 8) or (|dy| <= 1 and |dx| <= 8); kind 2 box -- x1 <= x <= x2, y1 <= y <= y2 and
+ * min(x - x1, x2 - x, y - y1, y2 - y) < 2 (an inverted box paints nothing); other kinds paint nothing. */
+int s2h_viz_compose(int n, int C, int H, int W, int img_kind, const void* frames, int64_t frame_stride,
+                    const void* frame0, const uint64_t* gt_words, const uint64_t* pred_words,
+                    const uint64_t* prompt_words, const uint8_t* palette, int M, const int* markers, uint8_t* out,
+                    hipStream_t st);
 /* The first upscaling step in one pass (mask_decoder.py:105-106, bf16, Co = 64): pre = the s2h_convt2_store
  * values, y / mean / rstd = LayerNorm2d(pre) over the channels (gamma, beta, eps; the values of
  * s2h_layernorm_fwd), post = gelu(y) (as s2h_act_fwd rounds it); mean / rstd [B * 2H * 2W] fp32. */

@@ -145,6 +145,8 @@ SIGNATURES = {
     "s2h_rle_transitions": [I, I, I, P, I, P, P, P, P],
     "s2h_label_hist": [I, I, I, P, P, P],
     "s2h_label_planes": [I, I, I, P, I, P, P, P, P],
+    "s2h_viz_pack": [I, I, I, I, I, P, L, P, P],
+    "s2h_viz_compose": [I, I, I, I, I, P, L, P, P, P, P, P, I, P, P, P],
     "s2h_resample_u8_norm": [I, I, I, P, I, I, P, P, P, I, I, P, P, P, I, I, P, P, P, P],
     "s2h_rle_catmasks": [I, I, I, I, I, P, P, P, P, I, I, P, P, P, P],
     "s2h_convt2_ln_gelu": [I, I, I, I, I, P, P, P, I, P, P, F, P, P, P, P, P, P],

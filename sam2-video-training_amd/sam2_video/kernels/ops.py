@@ -1865,6 +1865,60 @@ def mask_planes(mask_u8):
     return label_planes(mask_u8, frame_off, plane_class)
 
 
+# ---------------------------------------------------------------------- training visualisation (csrc/viz.hip)
+def _viz_frames(t, inner):
+    """(frame count, frame stride in elements) of a tensor whose frames are contiguous `inner`-shaped blocks"""
+    assert t.dim() == 1 + len(inner) and tuple(t.shape[1:]) == tuple(inner), (tuple(t.shape), inner)
+    assert t[0].is_contiguous() and (t.shape[0] == 1 or t.stride(0) >= 0)
+    return t.shape[0], (t.stride(0) if t.shape[0] > 1 else 0)
+
+
+def viz_pack(masks, out=None):
+    """category words of [n, C, H, W] masks (s2h_viz_pack): bit c of word [f, y, x] = masks[f, c, y, x] > 0.5.
+    uint8 / bool (set = non-zero) or fp32; each frame's [C, H, W] block contiguous, any frame stride >= 0 (a
+    strided slice of a clip is read where it lies).  -> int64 [n, H, W] holding the uint64 words."""
+    _dev(masks)
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    assert masks.dtype in (torch.uint8, torch.float32), masks.dtype
+    n, stride = _viz_frames(masks, masks.shape[1:])
+    _, C, H, W = masks.shape
+    if out is None:
+        out = torch.empty(n, H, W, device=masks.device, dtype=torch.int64)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == n * H * W
+    call("s2h_viz_pack", n, C, H, W, int(masks.dtype == torch.float32), ptr(masks), stride, ptr(out), stream())
+    return out
+
+
+def viz_compose(frames, frame0, gt_words, pred_words, palette, markers=None, prompt_words=None, out=None):
+    """the 2 x 2 composites uint8 [n, 2H, 2W, 3] (s2h_viz_compose; the picture is csrc/viz_pixel.h).
+    frames fp32 [n, 3, H, W] ImageNet-normalised or uint8 [n, H, W, 3], each frame contiguous, any frame stride;
+    frame0 one frame of the same kind; gt_words / pred_words int64 [n, H, W] from viz_pack; palette uint8 [C, 3];
+    markers int32 [M, 8] or None; prompt_words int64 [H, W] (mask prompts: no markers) or None."""
+    _dev(frames, frame0, gt_words, pred_words, palette, markers, prompt_words, out)
+    u8 = frames.dtype == torch.uint8
+    assert u8 or frames.dtype == torch.float32
+    n, H, W = gt_words.shape
+    inner = (H, W, 3) if u8 else (3, H, W)
+    nf, stride = _viz_frames(frames, inner)
+    assert nf == n and frame0.dtype == frames.dtype and tuple(frame0.shape) == inner and frame0.is_contiguous()
+    for w in (gt_words, pred_words):
+        assert w.dtype == torch.int64 and w.is_contiguous() and tuple(w.shape) == (n, H, W)
+    assert palette.dtype == torch.uint8 and palette.dim() == 2 and palette.shape[1] == 3 and palette.is_contiguous()
+    M = 0
+    if markers is not None and markers.numel():
+        assert markers.dtype == torch.int32 and markers.dim() == 2 and markers.shape[1] == 8 and markers.is_contiguous()
+        M = markers.shape[0]
+    if prompt_words is not None:
+        assert prompt_words.dtype == torch.int64 and prompt_words.is_contiguous() and prompt_words.numel() == H * W
+    if out is None:
+        out = torch.empty(n, 2 * H, 2 * W, 3, device=frames.device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n * 12 * H * W
+    call("s2h_viz_compose", n, palette.shape[0], H, W, int(u8), ptr(frames), stride, ptr(frame0), ptr(gt_words),
+         ptr(pred_words), ptr(prompt_words), ptr(palette), M, ptr(markers) if M else None, ptr(out), stream())
+    return out
+
+
 def convt2_gather(dout, B, H, W, Co, dY=None):
     if dY is None:
         dY = torch.empty(B * H * W, 4 * Co, device=dout.device, dtype=dout.dtype)

@@ -30,9 +30,17 @@ sam2_video/training/trainer.py:28-400) and a Lightning-API Trainer for them.
   graph per input signature), RCCL all-reduce + clip + AdamW at accumulation
   boundaries.
 
+* Visualisation (reference trainer.py:206-252 `_should_log_gif` / `_log_gif`): the reference's schedule
+  (`visualization.enabled`, `train_every_n_steps`, `val_first_batch_every_n_epochs`, `max_length`, `stride`,
+  `caption`) with a file sink instead of W&B: when the new key `visualization.save_dir` is set (default null:
+  nothing is rendered) a scheduled step composes the 2 x 2 frames on the device (utils/viz.py) and writes
+  `<save_dir>/{split}_e{epoch:04d}_s{global_step:07d}.gif` with Pillow.  Under StepRunner graphs the hook runs
+  after the replay, outside every capture, on the static batch, `last_outputs` and the prompt plan's host points;
+  it synchronises on the steps it fires and on no other.
+
 The reference's per-step torch.cuda.synchronize() + empty_cache()
 (trainer.py:186-187) are host syncs with no effect on results and are omitted.
-W&B GIF logging is out of scope.
+W&B itself is out of scope.
 """
 from __future__ import annotations
 
@@ -133,6 +141,7 @@ class SAM2LightningModule(_ModuleBase):
         self.gradient_clip_val = gradient_clip_val
         self.accumulate_grad_batches = accumulate_grad_batches
         self.compute_dtype = None  # set by the Trainer from `precision` (Lightning: setup reads it)
+        self.last_visualization: Optional[Dict[str, Any]] = None  # what _log_gif wrote last
 
     # ------------------------------------------------------------ setup
     def setup(self, stage: str = "fit", device=None):
@@ -340,7 +349,77 @@ class SAM2LightningModule(_ModuleBase):
             self.log(f"train/{k}", v)
         if self.optimizer is not None:
             self.log("train/learning_rate", self.optimizer.param_groups[0]["lr"])
+        # (a graph-replaying StepRunner runs the hook itself after the replay: this body is then a warm-up or a
+        # capture, and the captured outputs' point inputs are those of the first clip)
+        deferred = self.__dict__.get("_in_runner") and self.__dict__.get("_viz_deferred")
+        if not deferred and self._should_log_gif("train", batch_idx):
+            self._log_gif("train", batch.img_batch.squeeze(1), batch.masks, outs_per_frame, obj_to_cat, "train")
         return total
+
+    # --------------------------------------------------- visualisation
+    def _fit_trainer(self):
+        """the trainer of the running fit: Lightning's, or this build's (Trainer.fit sets `trainer_`)"""
+        return self._attached_trainer() or self.__dict__.get("trainer_")
+
+    def _batches_ready(self, tr) -> int:
+        """training batches started in this fit, the current one included (1 on the first): Lightning's
+        fit_loop.epoch_loop.batch_progress.total.ready; this build's Trainer counts epoch * batches per epoch +
+        the batch's index + 1 (both restored by a resume; the same number as the micro-step counter less the
+        padding of partial accumulation windows at epoch ends); a bare StepRunner its micro-steps"""
+        prog = getattr(getattr(getattr(tr, "fit_loop", None), "epoch_loop", None), "batch_progress", None)
+        if prog is not None:
+            return int(prog.total.ready)
+        if getattr(tr, "batches_ready", None) is not None:
+            return int(tr.batches_ready)
+        return int(self.__dict__.get("_viz_ready", 0))
+
+    def _should_log_gif(self, split: str, batch_idx: int) -> bool:
+        """trainer.py:206-223: never unless visualization.enabled and on global rank 0; train: every
+        train_every_n_steps-th started batch (0 = never); val: the first batch of every
+        val_first_batch_every_n_epochs-th epoch (0 = every epoch)"""
+        viz = self.cfg.visualization
+        if not _get(viz, "enabled", False):
+            return False
+        tr = self._fit_trainer()
+        zero = getattr(tr, "is_global_zero", None)
+        if zero is None:
+            import torch.distributed as dist
+            zero = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+        if not zero:
+            return False
+        if split == "train":
+            steps = int(_get(viz, "train_every_n_steps", 0) or 0)
+            return steps > 0 and self._batches_ready(tr) % steps == 0
+        if split == "val":
+            epochs = int(_get(viz, "val_first_batch_every_n_epochs", 0) or 0)
+            if epochs == 0:
+                return batch_idx == 0
+            return batch_idx == 0 and int(getattr(tr, "current_epoch", 0)) % epochs == 0
+        return False
+
+    def _log_gif(self, stage: str, frames, gt_masks, outs_per_frame, obj_to_cat, split: str):
+        """trainer.py:225-252 with a file in place of wandb.Video: nothing unless visualization.save_dir is set;
+        else the composites (device kernels, one copy back through the pinned staging buffer) go to
+        <save_dir>/{split}_e{epoch:04d}_s{global_step:07d}.gif at 4 fps with the reference's caption as the GIF
+        comment.  Never inside a stream capture."""
+        viz = self.cfg.visualization
+        save_dir = _get(viz, "save_dir")
+        if not save_dir or torch.cuda.is_current_stream_capturing():
+            return None
+        from ..utils import create_visualization_gif, save_visualization
+        gif = create_visualization_gif(frames=frames, gt_masks=gt_masks, outs_per_frame=outs_per_frame,
+                                       obj_to_cat=obj_to_cat, max_length=int(_get(viz, "max_length", 4)),
+                                       stride=int(_get(viz, "stride", 1)), to_host=True)
+        tr = self._fit_trainer()
+        # (a StepRunner driven without a Trainer: epoch 0 and the runner's own optimizer-step count)
+        epoch = int(getattr(tr, "current_epoch", 0))
+        step = int(getattr(tr, "global_step", self.__dict__.get("_viz_global_step", 0)))
+        caption = f"{_get(viz, 'caption', '')} | {split} e{epoch} s{step}"
+        path = os.path.join(str(save_dir), f"{split}_e{epoch:04d}_s{step:07d}.gif")
+        files = save_visualization(gif, path, fps=4, caption=caption, format=str(_get(viz, "format", "gif")))
+        self.last_visualization = {"stage": stage, "path": path, "files": files, "caption": caption,
+                                   "array": gif.copy()}  # (gif is a view of the reused staging buffer)
+        return path
 
     def _attached_trainer(self):
         """the Lightning trainer driving this module (LightningModule._trainer), if any; this
@@ -356,7 +435,7 @@ class SAM2LightningModule(_ModuleBase):
         was = self.model.training
         self.model.eval()
         try:
-            outs_per_frame, _ = self.forward(batch)
+            outs_per_frame, obj_to_cat = self.forward(batch)
             outs, targets = self._apply_gt_stride(outs_per_frame, batch.masks)
             losses = self.criterion(outs, targets)
         finally:
@@ -369,6 +448,8 @@ class SAM2LightningModule(_ModuleBase):
         self.last_eval = scores
         for k, v in scores["avg_scores"].items():
             self.log(f"val/{k}", v)
+        if self._should_log_gif("val", batch_idx):
+            self._log_gif("val", batch.img_batch.squeeze(1), batch.masks, outs_per_frame, obj_to_cat, "val")
         return losses[CORE_LOSS_KEY]
 
 
@@ -435,6 +516,9 @@ class StepRunner:
         # the backward's seed dL/dL: 1 (StepRunner), or the GradScaler scale of the Lightning path;
         # a device tensor read by the loss kernels' backward, so a captured graph picks up new values
         self.grad_seed = torch.ones((), device=arena.device, dtype=torch.float32)
+        # the visualisation hook of a graph-replayed step runs after the replay (_visualize), not in training_step
+        module._viz_deferred = bool(graph)
+        self._last_ent = None
         module.model.arena.zero_grad()
 
     def _device_step(self, batch):
@@ -533,6 +617,7 @@ class StepRunner:
             model.upload_prompt_plan(plan, dev, out=st.prompt_plan["dev"])
             st.prompt_plan.update({k: plan[k] for k in ("points", "labels")})
         ent["graph"].replay()
+        self._last_ent = ent
         self._segs = [(rep, rank) for rep, rank, _ in ent["segs"]]
         self.module.logged = dict(ent["logged"])
         self.module.last_outputs = ent["outputs"]
@@ -624,6 +709,8 @@ class StepRunner:
         boundary under DDP with the staged backward, each completed arena range is all-reduced beside
         the following segments (the works are waited for before this returns)"""
         self._segs = None
+        # (the batch and optimizer-step counts of a runner driven without a Trainer, for the visualisation)
+        self.module._viz_ready, self.module._viz_global_step = self.micro_step + 1, self.global_step
         loss = self._graphed_step(batch) if self.graph else self._device_step(batch)
         if self._segs is None:
             self._segs = self._segments()
@@ -643,7 +730,23 @@ class StepRunner:
             works += self.reducer.reduce_range(self.cuts[done], self.reducer.grad.numel())
             for w in works:
                 w.wait()
+        if self.graph:
+            self._visualize()
         return loss
+
+    def _visualize(self):
+        """the training visualisation of a graph-replayed micro-step, after its device work is issued and outside
+        every capture: the static batch, the outputs the replay just rewrote and the prompt plan's host points
+        (the captured outputs carry the first clip's)"""
+        m, ent = self.module, self._last_ent
+        if ent is None or not m._should_log_gif("train", self.micro_step):
+            return
+        st = ent["batch"]
+        plan = st.prompt_plan
+        outs = list(ent["outputs"])
+        if plan.get("points") is not None:
+            outs[0] = dict(outs[0], point_inputs={"point_coords": plan["points"], "point_labels": plan["labels"]})
+        m._log_gif("train", st.img_batch.squeeze(1), st.masks, outs, plan["obj_to_cat"], "train")
 
 
 def _static_batch(batch, device):
@@ -778,6 +881,7 @@ class Trainer:
         self.should_stop = False
         self.module = None
         self.runner = None
+        self.batches_ready = 0  # training batches started in this fit (the visualisation schedule's counter)
 
     # ---------------------------------------------------------------- callbacks
     def _first_callback(self, name):
@@ -945,6 +1049,7 @@ class Trainer:
                 if i >= n_train:
                     break
                 before = run.global_step
+                self.batches_ready = epoch * n_train + i + 1
                 run(_to_device(batch, device))
                 self.global_step = run.global_step
                 self._batches_done = i + 1
