@@ -712,6 +712,33 @@ int s2h_cc_components(int N, int H, int W, const int* labels, const int* areas, 
 int s2h_mask_rank_select(int Q, const int* q_img, const int* q_label, const int* q_neg, const int* q_rank, int N,
                          int H, int W, const int* labels, const uint8_t* grid, int* xy, int* count, int* work,
                          hipStream_t st);
+/* ---- correction clicks (reference sam2_video/model/modeling/sam2_utils.py:202-323 sample_random_points_from_errors
+ * and sample_one_point_from_error_center; csrc/clicks.hip).  Common to the three entries below: pure functions of
+ * their inputs, integer arithmetic only, no atomics, every device loop bounded independently of the data, no host
+ * round trip; 1 <= H, W <= 4092, H * W <= 2^24, N * H * W < 2^31 - 256 (B in place of N for the clicks).
+ *
+ * The exact squared Euclidean distance transform of byte masks [N, H, W] (nonzero = set) with the ring of pixels
+ * just outside the image counted as background: dist2(y, x) = 0 where the mask is clear, else the minimum of
+ * (y - y')^2 + (x - x')^2 over the (y', x') in [-1, H] x [-1, W] that lie outside the image or where the mask is
+ * clear -- the square of cv2.distanceTransform(np.pad(mask, 1), cv2.DIST_L2, 0)[1:-1, 1:-1].  dist2 int32
+ * [N, H, W].  work: 2 N H W bytes of scratch. */
+int s2h_edt_sq(int N, int H, int W, const uint8_t* mask, int* dist2, void* work, hipStream_t st);
+/* The click at the centre of the larger error region, per object b of B: FN = gt & ~pred, FP = ~gt & pred (gt,
+ * pred uint8 [B, H, W], nonzero = set; pred NULL = the empty prediction); (dn, in) = the maximum of the distance
+ * transform above of FN and the smallest row-major index that reaches it, (dp, ip) the same for FP; label 1 and
+ * index in when dn > dp, else label 0 and index ip.  points [B, 2] fp32 = (index % W, index / W); labels [B]
+ * int32; dmax [B, 2] int32 = (dn, dp).  Both regions empty: point (0, 0), label 0.  The distances are never
+ * written; the argmax is a maximum over the key (D2 << 32) | (0xFFFFFFFF - index), per workgroup and then over
+ * the workgroups' partials.  work: 16 B ceil(H W / 256) + 2 B H W bytes of scratch, 8-byte aligned. */
+int s2h_error_center_click(int B, int H, int W, const uint8_t* gt, const uint8_t* pred, float* points, int* labels,
+                           int* dmax, void* work, hipStream_t st);
+/* P uniformly drawn clicks in the error regions, per object b of B: R0 = FP | (all_correct & ~gt) (label 0), R1 =
+ * FN (label 1), all_correct = gt equals pred everywhere; n = |R0| + |R1|.  Click (b, p) is the
+ * ((r[b, p] mod 2^32) * n) >> 32 -th pixel of R0 | R1 in row-major order (64-bit product), its label says which set
+ * holds it; n = 0: point (0, 0), label 0.  r int64 [B, P] draws in [0, 2^32); points [B, P, 2] fp32 = (x, y);
+ * labels [B, P] int32; count [B, 2] int32 = (|R0|, |R1|).  work: 3 B (ceil(H W / 4096) + 1) int32 of scratch. */
+int s2h_error_uniform_click(int B, int P, int H, int W, const uint8_t* gt, const uint8_t* pred, const int64_t* r,
+                            float* points, int* labels, int* count, int* work, hipStream_t st);
 /* Category-merged masks of a tracked frame, bit-packed, without materialising the [N, H, W] logits
  * (reference sam2_video/eval/inference.py:487-514, per object `(out_mask_logits[i] > 0.0).cpu().numpy()` and
  * `torch.sigmoid(out_mask_logits[i]).mean().item()`, and :870-886, the `key % MOD` OR on the host).

@@ -34,6 +34,13 @@ np.random.choice calls in the reference's order, so both paths give the same pro
 eval/utils.py CLOSE_DILATE_WINDOW: it follows OpenCV's documented formulas, and the masks the reference's own
 cv2 opening wrote agree with it ("Dataset preparation on the device").
 
+Correction clicks (upstream's interactive protocol: prompt, then N corrective clicks, then track):
+add_correction_clicks compares the prompt frame's video-resolution logits with the objects' ground-truth masks
+and feeds the next click of every object back through add_new_points_or_box(clear_old_points=False), for
+`num_correction_clicks` rounds.  The clicks come from model/modeling/sam2_utils.py get_next_point -- on
+csrc/clicks.hip with `clicks_on_device=True`: one batched call and one copy of B clicks per round, where the
+reference's samplers copy two full-resolution masks per object to the host.  Off (0 clicks) by default.
+
 Out of scope: PromptObjNoiseAdder (`noised_prompt=True` raises: it needs albumentations) and the reference's
 dead helpers generate_negative_samples, fluctuate_point and get_obj_from_masks.
 """
@@ -99,6 +106,56 @@ def add_prompt(prompt_objs: List[PromptObj], predictor, inference_state, prompt_
         else:
             raise ValueError(f"unknown prompt type {prompt_type!r} (points, bbox or mask)")
     return predictor, inference_state, out_obj_ids, out_mask_logits
+
+
+def add_correction_clicks(prompt_objs: List[PromptObj], predictor, inference_state, frame_idx, out_mask_logits,
+                          n_clicks, method="center", on_device=True):
+    """n_clicks rounds of corrective clicks on one prompted frame: per round the frame's video-resolution logits
+    of all objects (out_mask_logits [N, 1, H, W], what add_prompt or the round before returned) are thresholded
+    at 0 and compared with the objects' ground truth (PromptObj.mask, uploaded once), get_next_point gives one
+    click per object in one batched call, the B clicks come to the host in one copy, and every object is refined
+    with add_new_points_or_box(clear_old_points=False).  The clicks are appended to each PromptObj's points /
+    pos_or_neg_label (so prompt.pkl records them).  method: "center" (the centre of the larger error region) or
+    "uniform" (a uniformly drawn error pixel; its generator is seeded from np.random.randint, so np.random.seed
+    fixes the run like the prompt draws).  on_device=False: the samplers' host twin.  -> the last logits"""
+    from ..model.modeling.sam2_utils import get_next_point
+    if method not in ("center", "uniform"):
+        raise ValueError(f"unknown sampling method {method}")
+    if n_clicks <= 0 or not prompt_objs:
+        return out_mask_logits
+    device = out_mask_logits.device
+    rows = [inference_state["obj_ids"].index(obj.obj_id) for obj in prompt_objs]
+    gt = torch.from_numpy(np.stack([np.asarray(obj.mask, dtype=bool) for obj in prompt_objs])[:, None]).to(device)
+    if gt.shape[-2:] != out_mask_logits.shape[-2:]:
+        raise ValueError(f"the ground-truth masks are {tuple(gt.shape[-2:])}, the video is "
+                         f"{tuple(out_mask_logits.shape[-2:])}")
+    generator = None
+    if method == "uniform":
+        generator = torch.Generator(device=device)
+        generator.manual_seed(int(np.random.randint(0, 2 ** 31 - 1)))
+    rows_d = torch.as_tensor(rows, device=device)
+    for _ in range(int(n_clicks)):
+        pred = out_mask_logits.index_select(0, rows_d) > 0
+        points, labels = get_next_point(gt, pred, method, generator=generator, on_device=on_device)
+        clicks = torch.cat([points.reshape(len(rows), 2), labels.reshape(len(rows), 1).to(torch.float32)],
+                           dim=1).cpu().numpy()  # the round's B clicks in one copy
+        for obj, (x, y, label) in zip(prompt_objs, clicks):
+            _, _, out_mask_logits = predictor.add_new_points_or_box(
+                inference_state=inference_state, frame_idx=frame_idx, obj_id=obj.obj_id,
+                points=np.array([[x, y]], dtype=np.float32), labels=np.array([label], dtype=np.int32),
+                clear_old_points=False)
+            pts = np.asarray(obj.points)
+            obj.points = np.concatenate([pts.reshape(-1, 2), np.array([[x, y]]).astype(pts.dtype)], axis=0)
+            lab = np.asarray(obj.pos_or_neg_label)
+            obj.pos_or_neg_label = np.concatenate([lab, np.array([label]).astype(lab.dtype)])
+    return out_mask_logits
+
+
+def _check_clicks(prompt_type, num_correction_clicks):
+    if num_correction_clicks and PROMPT_TYPES.get(prompt_type, prompt_type) == "mask":
+        raise ValueError("correction clicks with the mask prompt type: the prompt already is the ground truth")
+    if num_correction_clicks < 0:
+        raise ValueError(f"num_correction_clicks is {num_correction_clicks}")
 
 
 def predict_on_video(predictor, inference_state, start_idx, frames=None, probs_out_dir: Optional[str] = None, *,
@@ -211,11 +268,16 @@ def _read_frames(paths) -> np.ndarray:
 def process_video_clip(predictor, frames, clip_prompts: List[PromptInfo], clip_range: ClipRange,
                        probs_out_dir: Optional[str] = None, *, video=None, mod: Optional[int] = None,
                        export_on_device: bool = True, finetuned_state_dict=None, threshold: Optional[float] = None,
-                       sweep=None) -> Dict:
+                       sweep=None, num_correction_clicks: int = 0, correction_method: str = "center",
+                       clicks_on_device: bool = True) -> Dict:
     """inference.py:532-577 on a predictor the caller built: init_state on the clip's frames, the clip's
     prompts, predict_on_video.  `frames`: the video's frame dicts (id, video_id, order_in_video, height,
     width, path), indexed by order_in_video as in the reference.  `video`: the clip's images as a list of
-    paths, a JPEG folder or a [T, H, W, 3] uint8 array; default: the `path` of frames[start_idx:end_idx + 1]."""
+    paths, a JPEG folder or a [T, H, W, 3] uint8 array; default: the `path` of frames[start_idx:end_idx + 1].
+    num_correction_clicks > 0: every prompt frame's objects get that many corrective clicks before tracking
+    (add_correction_clicks; correction_method center | uniform, clicks_on_device False = the host twin)."""
+    for prompt_info in clip_prompts:
+        _check_clicks(prompt_info.prompt_type, num_correction_clicks)
     start_idx, end_idx = clip_range.start_idx, clip_range.end_idx
     if video is None:
         video = [f["path"] for f in frames[start_idx:end_idx + 1]]
@@ -225,8 +287,12 @@ def process_video_clip(predictor, frames, clip_prompts: List[PromptInfo], clip_r
         _load_finetuned_weights_into_predictor(predictor, finetuned_state_dict)
     inference_state = predictor.init_state(video_path=video)
     for prompt_info in clip_prompts:
-        add_prompt(prompt_info.prompt_objs, predictor, inference_state, prompt_info.frame_idx - start_idx,
-                   prompt_info.prompt_type)
+        _, _, _, logits = add_prompt(prompt_info.prompt_objs, predictor, inference_state,
+                                     prompt_info.frame_idx - start_idx, prompt_info.prompt_type)
+        if num_correction_clicks:
+            add_correction_clicks(prompt_info.prompt_objs, predictor, inference_state,
+                                  prompt_info.frame_idx - start_idx, logits, num_correction_clicks,
+                                  method=correction_method, on_device=clicks_on_device)
     return predict_on_video(predictor, inference_state, start_idx, frames=frames, probs_out_dir=probs_out_dir,
                             mod=mod, export_on_device=export_on_device, threshold=threshold, sweep=sweep)
 
@@ -569,7 +635,9 @@ def merge_prompts(prompts_by_categories: Iterable, prompts_by_clip_length: Itera
 
 def process_singel_video(predictor, gen: PromptGen, frames, prompt_type, clip_length: Optional[int] = None,
                          variable_cats: bool = False, probs_out_dir=None, *, prompt_log: Optional[List] = None,
-                         export_on_device: bool = True, threshold: Optional[float] = None, sweep=None) -> Dict:
+                         export_on_device: bool = True, threshold: Optional[float] = None, sweep=None,
+                         num_correction_clicks: int = 0, correction_method: str = "center",
+                         clicks_on_device: bool = True) -> Dict:
     """inference.py:771-814 (the reference's spelling): the object count restarts, the video's clips are prompted
     and tracked one after the other on `predictor`; every clip's PromptInfo list is appended to prompt_log"""
     gen.obj_count = 0
@@ -584,17 +652,23 @@ def process_singel_video(predictor, gen: PromptGen, frames, prompt_type, clip_le
             prompt_log.extend(clip_prompts)
         video_segments.update(process_video_clip(predictor, frames, clip_prompts, clip_range,
                                                  probs_out_dir=probs_out_dir, mod=gen.coco.mod,
-                                                 export_on_device=export_on_device, threshold=threshold, sweep=sweep))
+                                                 export_on_device=export_on_device, threshold=threshold, sweep=sweep,
+                                                 num_correction_clicks=num_correction_clicks,
+                                                 correction_method=correction_method,
+                                                 clicks_on_device=clicks_on_device))
     return video_segments
 
 
 def process_all_videos(predictor, gen: PromptGen, prompt_type, clip_length, variable_cats, probs_out_dir=None, *,
                        prompt_log: Optional[List] = None, export_on_device: bool = True,
-                       threshold: Optional[float] = None, sweep=None) -> Dict:
+                       threshold: Optional[float] = None, sweep=None, num_correction_clicks: int = 0,
+                       correction_method: str = "center", clicks_on_device: bool = True) -> Dict:
     """inference.py:818-841: {video_id: process_singel_video's result}, the videos in first-seen order"""
     return {video_id: process_singel_video(predictor, gen, gen.coco.frames(video_id), prompt_type, clip_length,
                                            variable_cats, probs_out_dir=probs_out_dir, prompt_log=prompt_log,
-                                           export_on_device=export_on_device, threshold=threshold, sweep=sweep)
+                                           export_on_device=export_on_device, threshold=threshold, sweep=sweep,
+                                           num_correction_clicks=num_correction_clicks,
+                                           correction_method=correction_method, clicks_on_device=clicks_on_device)
             for video_id in gen.coco.video_ids()}
 
 
@@ -603,7 +677,8 @@ def inference(coco_path, output_path, prompt_type, save_video_list=None, clip_le
               bbox_noise_type="shift_scale", num_neg_points=0, grid_spaceing=None, probs_out_dir: Optional[str] = None,
               *, run_dir, model_cfg_override: Optional[str] = None, sam2_checkpoint_override: Optional[str] = None,
               finetuned_state_dict=None, predictor=None, prompts_on_device: bool = True,
-              export_on_device: bool = True, threshold: Optional[float] = None, sweep=None):
+              export_on_device: bool = True, threshold: Optional[float] = None, sweep=None,
+              num_correction_clicks: int = 0, correction_method: str = "center", clicks_on_device: bool = True):
     """inference.py:919-1085: prompts from the ground truth of `coco_path` (a COCO file whose images carry
     video_id, order_in_video, is_det_keyframe, path, height and width), every video tracked clip by clip,
     `<run_dir>/eval/predict.json` and `prompt.pkl` written -> (predict path, prompt path).  prompt_type: point |
@@ -614,7 +689,10 @@ def inference(coco_path, output_path, prompt_type, save_video_list=None, clip_le
 
     Beyond the reference: predictor (None: built once with build_sam2_video_predictor from model_cfg_override /
     sam2_checkpoint_override or the module's MODEL_CFG / SAM2_CHECKPOINT, and reused for every clip);
-    prompts_on_device (get_each_obj on the HIP kernels); export_on_device, threshold, sweep: see predict_on_video.
+    prompts_on_device (get_each_obj on the HIP kernels); export_on_device, threshold, sweep: see predict_on_video;
+    num_correction_clicks (0: none), correction_method (center | uniform), clicks_on_device: every prompt frame's
+    objects get that many corrective clicks against their ground truth before the clip is tracked
+    (add_correction_clicks); with the mask prompt type a nonzero count raises ValueError.
 
     Differences from the reference: the predictor is built (and finetuned_state_dict loaded) once, not per clip;
     the videos are processed in first-seen order (the reference iterates a set); prompt.pkl holds this call's
@@ -627,6 +705,9 @@ def inference(coco_path, output_path, prompt_type, save_video_list=None, clip_le
                                   "and is not part of this package")
     if run_dir is None or str(run_dir).strip() == "":
         raise ValueError("inference(): run_dir must be provided and non-empty")
+    _check_clicks(prompt_type, num_correction_clicks)
+    if correction_method not in ("center", "uniform"):
+        raise ValueError(f"unknown sampling method {correction_method}")
     eval_dir = os.path.join(str(run_dir), "eval")
     os.makedirs(eval_dir, exist_ok=True)
     coco = CocoIndex(coco_path)
@@ -648,7 +729,9 @@ def inference(coco_path, output_path, prompt_type, save_video_list=None, clip_le
     prompt_log: List[PromptInfo] = []
     segments = process_all_videos(predictor, gen, PROMPT_TYPES.get(prompt_type, prompt_type), clip_length,
                                   variable_cats, probs_out_dir=probs_out_dir, prompt_log=prompt_log,
-                                  export_on_device=export_on_device, threshold=threshold, sweep=sweep)
+                                  export_on_device=export_on_device, threshold=threshold, sweep=sweep,
+                                  num_correction_clicks=num_correction_clicks, correction_method=correction_method,
+                                  clicks_on_device=clicks_on_device)
     frames_by_video = {video_id: coco.frames(video_id) for video_id in coco.video_ids()}
     paths = save_as_coco_format(segments, frames_by_video, coco.mod, eval_dir, prompt_info=prompt_log,
                                 save_video_list=save_video_list)

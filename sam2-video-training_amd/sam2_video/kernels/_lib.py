@@ -139,6 +139,9 @@ SIGNATURES = {
     "s2h_morph_rect": [I, I, I, P, I, I, I, I, I, P, P, P],
     "s2h_cc_components": [I, I, I, P, P, I, P, I, P, P, P, P, P],
     "s2h_mask_rank_select": [I, P, P, P, P, I, I, I, P, P, P, P, P, P],
+    "s2h_edt_sq": [I, I, I, P, P, P, P],
+    "s2h_error_center_click": [I, I, I, P, P, P, P, P, P, P],
+    "s2h_error_uniform_click": [I, I, I, I, P, P, P, P, P, P, P, P],
     "s2h_mask_export": [I, I, I, I, I, P, I, P, P, I, P, P, P, P],
     "s2h_mask_export_cut": [I, I, I, I, I, P, I, P, P, I, F, P, P, P, P, P],
     "s2h_mask_sweep": [I, I, I, I, I, P, I, P, P, I, I, P, P, P, P],

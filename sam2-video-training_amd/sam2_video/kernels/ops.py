@@ -1688,6 +1688,69 @@ def mask_rank_select(q_img, q_label, q_neg, q_rank, labels, grid=None):
     return xy, count
 
 
+# ------------------------------------------------------------------ correction clicks (csrc/clicks.hip)
+CK_MAX_SIDE = 4092  # H, W of the three entries below (csrc/clicks.h): keeps D2 < 2^22
+
+
+def _click_masks(gt, pred):
+    assert gt.dim() == 3 and gt.dtype == torch.uint8 and gt.is_contiguous()
+    _dev(gt)
+    if pred is not None:
+        assert pred.shape == gt.shape and pred.dtype == torch.uint8 and pred.is_contiguous()
+        _dev(pred)
+    B, H, W = gt.shape
+    if not (1 <= H <= CK_MAX_SIDE and 1 <= W <= CK_MAX_SIDE):
+        raise ValueError(f"masks of {H} x {W}: both sides must be in [1, {CK_MAX_SIDE}]")
+    return B, H, W
+
+
+def edt_sq(mask):
+    """exact squared Euclidean distance transform of byte masks [N, H, W] (nonzero = set), the ring of pixels
+    just outside the image counted as background (s2h_edt_sq): 0 where the mask is clear, else the smallest
+    squared distance to a clear or outside pixel.  -> int32 [N, H, W]"""
+    N, H, W = _click_masks(mask, None)
+    dist2 = torch.empty(N, H, W, device=mask.device, dtype=torch.int32)
+    work = torch.empty(max(1, N * H * W), device=mask.device, dtype=torch.int16)
+    call("s2h_edt_sq", N, H, W, ptr(mask), ptr(dist2), ptr(work), stream())
+    return dist2
+
+
+def error_center_click(gt, pred=None):
+    """per object the click at the centre of the larger error region (s2h_error_center_click): gt, pred uint8
+    [B, H, W] (nonzero = set; pred None = the empty prediction).  -> (points fp32 [B, 2] = (x, y), labels int32
+    [B]: 1 in the missed region, 0 in the wrongly predicted one, dmax int32 [B, 2]: the largest squared distance
+    inside the missed and inside the wrongly predicted region)"""
+    B, H, W = _click_masks(gt, pred)
+    dev = gt.device
+    points = torch.empty(B, 2, device=dev, dtype=torch.float32)
+    labels = torch.empty(B, device=dev, dtype=torch.int32)
+    dmax = torch.empty(B, 2, device=dev, dtype=torch.int32)
+    nb = (H * W + 255) // 256
+    work = torch.empty(max(1, 2 * B * nb + (B * H * W + 3) // 4), device=dev, dtype=torch.int64)
+    call("s2h_error_center_click", B, H, W, ptr(gt), ptr(pred), ptr(points), ptr(labels), ptr(dmax), ptr(work),
+         stream())
+    return points, labels, dmax
+
+
+def error_uniform_click(gt, pred, r):
+    """per object P clicks drawn uniformly from the error regions, or from the background when there is no error
+    (s2h_error_uniform_click): gt, pred as error_center_click; r int64 [B, P] draws in [0, 2^32): click (b, p) is
+    the (r n) >> 32 -th of the n candidate pixels in row-major order.  -> (points fp32 [B, P, 2] = (x, y), labels
+    int32 [B, P], count int32 [B, 2] = the candidates of label 0 and of label 1)"""
+    B, H, W = _click_masks(gt, pred)
+    assert r.dim() == 2 and r.shape[0] == B and r.dtype == torch.int64 and r.is_contiguous()
+    _dev(r)
+    P = r.shape[1]
+    dev = gt.device
+    points = torch.empty(B, P, 2, device=dev, dtype=torch.float32)
+    labels = torch.empty(B, P, device=dev, dtype=torch.int32)
+    count = torch.empty(B, 2, device=dev, dtype=torch.int32)
+    work = torch.empty(max(1, 3 * B * ((H * W + GP_CHUNK - 1) // GP_CHUNK + 1)), device=dev, dtype=torch.int32)
+    call("s2h_error_uniform_click", B, P, H, W, ptr(gt), ptr(pred), ptr(r), ptr(points), ptr(labels), ptr(count),
+         ptr(work), stream())
+    return points, labels, count
+
+
 RLE_HDR = 8  # int32 per category of s2h_rle_transitions' header (csrc/rle_scan.h)
 
 

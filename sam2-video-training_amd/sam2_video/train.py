@@ -20,8 +20,9 @@ it is under Hydra.
 Then the post-training block (train.py:135-231), when `eval.enabled` is set and `eval.coco_path`
 exists: the best checkpoint (`trainer.checkpoint_callback.best_model_path`, `model.` prefix
 stripped; none = the untuned weights, as the reference) -> `inference()` with the reference's
-argument mapping -> `eval()` -> <run_dir>/eval/metrics.json (eval/mIoU, eval/Dice, eval/MAE,
-best_checkpoint_path; with `eval.log_per_category` also eval/cat/<id>/{IoU,Dice,MAE}, which the
+argument mapping (plus the optional `eval.num_correction_clicks` / `eval.correction_method`, this
+build's corrective clicks before tracking) -> `eval()` -> <run_dir>/eval/metrics.json (eval/mIoU,
+eval/Dice, eval/MAE, best_checkpoint_path; with `eval.log_per_category` also eval/cat/<id>/{IoU,Dice,MAE}, which the
 reference sends to W&B only).  Unlike the reference, which raises, a missing `eval` section or an
 enabled one whose COCO file does not exist prints one line to stderr and skips the block:
 synthetic-data runs have no COCO file.  W&B logging and the baseline deltas
@@ -123,7 +124,9 @@ def post_training_eval(cfg, trainer, run_dir):
         noise_intensity=ev.get("noise_intensity", 0.1), bbox_noise_type=ev.get("bbox_noise_type", "shift_scale"),
         num_neg_points=ev.get("num_neg_points", 0), grid_spaceing=ev.get("grid_spacing"),
         save_video_list=ev.get("save_video_list"), model_cfg_override=model.get("config_path"),
-        sam2_checkpoint_override=model.get("checkpoint_path"), finetuned_state_dict=best_state_dict)
+        sam2_checkpoint_override=model.get("checkpoint_path"), finetuned_state_dict=best_state_dict,
+        num_correction_clicks=int(ev.get("num_correction_clicks", 0) or 0),
+        correction_method=ev.get("correction_method", "center"))
     eval_dir = os.path.join(str(run_dir), "eval")
     os.makedirs(eval_dir, exist_ok=True)
     eval_eval.eval(predict_path=os.path.join(eval_dir, "predict.json"), coco_path=coco_path, output_path=eval_dir)
